@@ -7,7 +7,19 @@ Contract (driver): `python bench.py --gpus N --steps K --warmup W`; for N>1
 launched via torch.distributed.run with one rank per GPU over RCCL.  W
 untimed warmup steps, then exactly K timed steps bracketed by barrier +
 synchronize on both sides; elapsed is MAX over ranks; rank 0 prints ONE JSON
-line.
+line.  A plain run does only that: set up, warm up, time the K steps, print.
+Every other measurement is chosen explicitly (``--mode``, ``--model``,
+``--hipgraph``); ``--full`` is the switch for secondary measurements that ride
+along with the headline run (none exist today, so it changes nothing yet).
+
+``--dump-outputs DIR`` writes, after the timed steps, ``DIR/<name>.npy``
+(float32, or float64 for integer buffers and the scalar losses).  Training
+modes: ``loss``, what the last timed step returned, and ``ref.*``: loss,
+gradients and weights of one more, untimed step that the same trainer takes
+on the same batch after being rewound to its seeded initial state (see
+``timed_path_outputs`` for why not the weights after the timed steps).
+``--mode infer``: the logits of the last timed step.  Seeds are fixed, so the
+inputs are identical from run to run with the same arguments.
 
 The timed step is the full training step: zero -> fwd (fused MFMA linear+
 relu) -> fused CE (loss+dlogits one kernel) -> bwd (MFMA dgrad/wgrad,
@@ -27,6 +39,81 @@ import time
 import torch
 import torch.distributed as dist
 import torch.nn as nn
+
+
+DUMP_BUDGET_BYTES = 64 * 1000 * 1000  # cap on everything --dump-outputs writes
+
+
+def initial_state(trainer) -> dict:
+    """Copy of the trainer's weights and buffers, taken before the first step."""
+    return {k: v.detach().clone() for k, v in trainer.model.state_dict().items()}
+
+
+def timed_path_outputs(trainer, init_state, last_loss, x, y) -> dict:
+    """What ``--dump-outputs`` writes for the training modes.
+
+    ``loss``: the value the last timed ``train_step`` returned.
+
+    ``ref.*``: the timed trainer itself — same object, buckets, optimizer,
+    captured graph — is rewound in place to ``init_state`` with zeroed Adam
+    moments and step counter, and takes one more, untimed ``train_step`` on the
+    same batch; its loss, the gradients it leaves and the weights after it are
+    written.  Anything the timed steps left behind in the trainer that a step
+    should not depend on (stale buffers, missed zeroing, caches) shows here.
+
+    The weights the timed steps end in are not written, because they do not
+    repeat from run to run: the split-K wgrad, bias-grad and loss kernels
+    accumulate with fp32 atomics, so one step repeats only to rounding (~3e-7
+    on the weights), and Adam on this batch (random labels; the gradients are
+    cancellation noise) multiplies that by orders of magnitude per step.  Two
+    identical runs on one MI355X differ by 8% of the largest weight after 25
+    steps; the loss still agrees to 2e-6 there and to 6e-4 after 200 steps.
+    Collective when world > 1: every rank must call it."""
+    opt = trainer.optimizer
+    if opt is None or not hasattr(opt, "exp_avg"):
+        raise RuntimeError("--dump-outputs rewinds the fused Adam state; no fused Adam on this trainer")
+    with torch.no_grad():
+        trainer.model.load_state_dict(init_state)
+        opt.step_count = 0
+        for t in list(opt.exp_avg) + list(opt.exp_avg_sq):
+            t.zero_()
+        if opt.step_dev is not None:
+            opt.step_dev.zero_()
+    ref_loss = trainer.train_step(x, y)
+    outs = {"loss": torch.tensor([last_loss], dtype=torch.float64),
+            "ref.loss": torch.tensor([ref_loss], dtype=torch.float64)}
+    for k, p in trainer.model.named_parameters():
+        if p.grad is not None:
+            outs["ref.grad." + k] = p.grad
+    for k, v in trainer.model.state_dict().items():
+        outs["ref.state." + k] = v
+    return outs
+
+
+def dump_outputs(dirname: str, tensors: dict) -> None:
+    """Write each tensor as ``dirname/<name>.npy``: float32 for floating
+    tensors, float64 for float64/integer ones.  If the total would exceed
+    DUMP_BUDGET_BYTES every array is cut to the same fraction of its elements,
+    picked by a fixed-seed sample of the flattened array (sorted indices), so
+    two runs dump the same positions."""
+    import numpy as np
+
+    os.makedirs(dirname, exist_ok=True)
+    arrays = {}
+    for name, t in tensors.items():
+        t = t.detach()
+        wide = t.dtype == torch.float64 or not t.dtype.is_floating_point
+        arrays[name] = t.to("cpu", torch.float64 if wide else torch.float32).numpy()
+    # .npy headers are ~128 bytes each; leave room for them
+    budget = DUMP_BUDGET_BYTES - 256 * len(arrays)
+    total = sum(a.nbytes for a in arrays.values())
+    frac = min(1.0, budget / max(1, total))
+    for i, (name, a) in enumerate(sorted(arrays.items())):
+        if frac < 1.0 and a.size > 1:
+            keep = max(1, int(a.size * frac))
+            idx = np.sort(np.random.default_rng(i).choice(a.size, keep, replace=False))
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(dirname, name + ".npy"), np.ascontiguousarray(a))
 
 
 def main() -> int:
@@ -53,7 +140,19 @@ def main() -> int:
                          "included), then runs the training iterations")
     ap.add_argument("--target-loss", type=float, default=1.0)
     ap.add_argument("--max-steps", type=int, default=2000)
+    ap.add_argument("--full", action="store_true",
+                    help="also run the secondary measurements that accompany the "
+                         "headline figure (none today: a plain run is already only "
+                         "setup, warmup, the timed steps and the result line)")
+    ap.add_argument("--dump-outputs", type=str, default=None, metavar="DIR",
+                    help="after the timed steps write DIR/<name>.npy: the last timed "
+                         "step's loss, plus loss, gradients and weights of one more "
+                         "untimed step of the same trainer rewound to its seeded "
+                         "initial state (training modes); the last step's logits "
+                         "(--mode infer)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be >= 1")
 
     if args.mode == "fit" and args.batch == 0 and args.model == "mnist_mlp":
         # fit mode materializes per-row fp64 Vector objects; 131072 rows is
@@ -144,15 +243,21 @@ def main() -> int:
         if on_gpu:
             torch.cuda.synchronize()
 
+    init_state = initial_state(trainer) if args.dump_outputs else None
     for _ in range(args.warmup):
         trainer.train_step(x, y)
 
     barrier_sync()
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        trainer.train_step(x, y)
+        loss = trainer.train_step(x, y)
     barrier_sync()
     elapsed = time.perf_counter() - t0
+
+    if args.dump_outputs:
+        outs = timed_path_outputs(trainer, init_state, loss, x, y)
+        if rank == 0:
+            dump_outputs(args.dump_outputs, outs)
 
     # max over ranks
     if world > 1:
@@ -220,6 +325,7 @@ def run_fit(args, model, device, on_gpu, world, rank) -> int:
 
     opt = torch.optim.Adam(model.parameters(), lr=1e-3)
     trainer = SyncTrainer(model, nn.CrossEntropyLoss(), opt, device=device, world_size=world)
+    init_state = initial_state(trainer) if args.dump_outputs else None
 
     def ingest():
         if on_gpu:
@@ -247,12 +353,17 @@ def run_fit(args, model, device, on_gpu, world, rank) -> int:
         torch.cuda.synchronize()
     t_ingest = time.perf_counter() - t0
     for _ in range(args.steps):
-        trainer.train_step(x, y)
+        loss = trainer.train_step(x, y)
     if world > 1:
         dist.barrier()
     if on_gpu:
         torch.cuda.synchronize()
     elapsed = time.perf_counter() - t0
+
+    if args.dump_outputs:
+        outs = timed_path_outputs(trainer, init_state, loss, x, y)
+        if rank == 0:
+            dump_outputs(args.dump_outputs, outs)
 
     if world > 1:
         et = torch.tensor([elapsed], device=device if on_gpu else "cpu")
@@ -291,6 +402,7 @@ def run_time_to_loss(args, model, device, on_gpu, world, rank) -> int:
 
     opt = torch.optim.Adam(model.parameters(), lr=1e-3)
     trainer = SyncTrainer(model, nn.CrossEntropyLoss(), opt, device=device, world_size=world)
+    init_state = initial_state(trainer) if args.dump_outputs else None
     in_dim = 3 * 224 * 224 if args.model == "resnet18" else 784
     n_classes = 1000 if args.model == "resnet18" else 10
     torch.manual_seed(1234 + rank)
@@ -320,6 +432,10 @@ def run_time_to_loss(args, model, device, on_gpu, world, rank) -> int:
     if on_gpu:
         torch.cuda.synchronize()
     elapsed = time.perf_counter() - t0
+    if args.dump_outputs:
+        outs = timed_path_outputs(trainer, init_state, loss, x, y)
+        if rank == 0:
+            dump_outputs(args.dump_outputs, outs)
     if rank == 0:
         print(json.dumps({
             "metric": "time_to_loss_s",
@@ -360,12 +476,12 @@ def run_infer(args, model, device, on_gpu) -> int:
         x = x.to(torch.bfloat16)
 
         def step():
-            runner.replay_device(x)
+            return runner.replay_device(x)
         step()  # capture
     else:
         def step():
             with torch.no_grad():
-                model(x)
+                return model(x)
 
     for _ in range(args.warmup):
         step()
@@ -373,10 +489,12 @@ def run_infer(args, model, device, on_gpu) -> int:
         torch.cuda.synchronize()
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        step()
+        logits = step()
     if on_gpu:
         torch.cuda.synchronize()
     elapsed = time.perf_counter() - t0
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"logits": logits})
     out = {
         "metric": "inference_samples_per_sec",
         "value": bs * args.steps / elapsed,

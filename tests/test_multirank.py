@@ -122,7 +122,8 @@ def test_bench_torchrun_contract_gloo(world, tmp_path):
          "--nnodes=1", "--nproc-per-node", str(world),
          "--master-addr", "127.0.0.1", "--master-port", str(port),
          os.path.join(REPO, "bench.py"),
-         "--gpus", str(world), "--steps", "3", "--warmup", "1", "--batch", "512"],
+         "--gpus", str(world), "--steps", "3", "--warmup", "1", "--batch", "512",
+         "--device", "cpu"],  # gloo also where a GPU is visible (one card, N ranks)
         capture_output=True,
         text=True,
         timeout=420,
@@ -150,7 +151,8 @@ def test_bench_time_to_loss_world2_no_deadlock(tmp_path):
          "--master-addr", "127.0.0.1", "--master-port", str(port),
          os.path.join(REPO, "bench.py"),
          "--mode", "time_to_loss", "--batch", "1024",
-         "--max-steps", "30", "--target-loss", "2.1"],
+         "--max-steps", "30", "--target-loss", "2.1",
+         "--device", "cpu"],  # gloo also where a GPU is visible (one card, 2 ranks)
         capture_output=True,
         text=True,
         timeout=420,
