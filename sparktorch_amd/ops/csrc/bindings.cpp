@@ -42,6 +42,12 @@ hipError_t launch_mse_fused(const bf16raw*, const bf16raw*, float*, bf16raw*, in
 hipError_t launch_gemm_bf16(const void*, const void*, int, float*, bf16raw*, const float*, int,
                             int, int, int64_t, int64_t, int64_t, int64_t, int, int, float*, int,
                             hipStream_t);
+hipError_t launch_gemm_bf16_mask(const void*, const void*, int, float*, bf16raw*, const float*,
+                                 int, int, int, int64_t, int64_t, int64_t, int64_t, int, int,
+                                 float*, int, const bf16raw*, hipStream_t);
+int head_bwd_supported(int, int);
+hipError_t launch_head_bwd(const bf16raw*, const bf16raw*, const bf16raw*, bf16raw*, float*,
+                           float*, int, int, int, int, int, hipStream_t);
 hipError_t launch_bn_stats(const bf16raw*, float*, float*, float*, float*, float*, float*, int,
                            int, int64_t, float, float, int, hipStream_t);
 hipError_t launch_bn_apply(const bf16raw*, const bf16raw*, bf16raw*, const float*, const float*,
@@ -338,6 +344,73 @@ at::Tensor linear_dgrad(at::Tensor dz, at::Tensor w) {
                              nullptr, (bf16raw*)dx.data_ptr(), nullptr, (int)M, (int)K, (int)N,
                              /*sam*/ N, /*sak*/ 1, /*sbk*/ K, /*sbn*/ 1, 1, 1, nullptr, -1, cur_stream()));
   return dx;
+}
+
+// dX = (dZ W) * (y_prev > 0): linear_dgrad with the producer layer's ReLU
+// backward folded into the C-write (gemm.hip EPI_BF16_MASK); bit-identical
+// to relu_bwd(linear_dgrad(dz, w), y_prev).
+at::Tensor linear_dgrad_relu(at::Tensor dz, at::Tensor w, at::Tensor y_prev) {
+  check_gpu_contig(dz, at::kBFloat16, "dz");
+  check_gpu_contig(y_prev, at::kBFloat16, "y_prev");
+  TORCH_CHECK(w.is_cuda() && w.is_contiguous());
+  int64_t M = dz.size(0), N = dz.size(1), K = w.size(1);
+  TORCH_CHECK(w.size(0) == N, "shape mismatch");
+  TORCH_CHECK(y_prev.dim() == 2 && y_prev.size(0) == M && y_prev.size(1) == K,
+              "y_prev must be [M, K_in]");
+  auto dx = at::empty({M, K}, dz.options());
+  CHECK_HIP(launch_gemm_bf16_mask(dz.data_ptr(), w.data_ptr(),
+                                  w.scalar_type() == at::kFloat ? 1 : 0, nullptr,
+                                  (bf16raw*)dx.data_ptr(), nullptr, (int)M, (int)K, (int)N,
+                                  /*sam*/ N, /*sak*/ 1, /*sbk*/ K, /*sbn*/ 1, 6, 1, nullptr, -1,
+                                  (const bf16raw*)y_prev.data_ptr(), cur_stream()));
+  return dx;
+}
+
+// One-pass backward of a <=16-class head on a ReLU layer (head_bwd.hip):
+// returns dz_in = (dz_out @ w) * (y_in > 0); dw / db are accumulated into
+// (the caller owns the zeroing, as with linear_wgrad_bias_into).
+bool head_bwd_ok(int64_t C, int64_t H) { return head_bwd_supported((int)C, (int)H) != 0; }
+
+static int head_num_cus() {
+  static int cus[64] = {};
+  int dev = 0;
+  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return 256;
+  if (cus[dev] == 0) {
+    int n = 0;
+    if (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess ||
+        n <= 0)
+      n = 256;
+    cus[dev] = n;
+  }
+  return cus[dev];
+}
+
+at::Tensor linear_head_bwd(at::Tensor dz_out, at::Tensor w, at::Tensor y_in, at::Tensor dw,
+                           c10::optional<at::Tensor> db, int64_t max_blocks) {
+  check_gpu_contig(dz_out, at::kBFloat16, "dz_out");
+  check_gpu_contig(w, at::kBFloat16, "w");
+  check_gpu_contig(y_in, at::kBFloat16, "y_in");
+  check_gpu_contig(dw, at::kFloat, "dw");
+  TORCH_CHECK(dz_out.dim() == 2 && w.dim() == 2 && y_in.dim() == 2);
+  int64_t B = dz_out.size(0), C = dz_out.size(1), H = w.size(1);
+  TORCH_CHECK(B >= 1 && B < (1LL << 31) && w.size(0) == C && y_in.size(0) == B &&
+                  y_in.size(1) == H && dw.size(0) == C && dw.size(1) == H,
+              "shape mismatch");
+  TORCH_CHECK(head_bwd_ok(C, H), "linear_head_bwd: unsupported (C, H); use the per-layer route");
+  float* dbp = nullptr;
+  if (db.has_value()) {
+    check_gpu_contig(*db, at::kFloat, "db");
+    TORCH_CHECK(db->numel() == C);
+    dbp = db->data_ptr<float>();
+  }
+  auto dz_in = at::empty({B, H}, y_in.options());
+  TORCH_CHECK(((uintptr_t)y_in.data_ptr() & 15) == 0 && ((uintptr_t)dz_in.data_ptr() & 15) == 0,
+              "linear_head_bwd wants 16-byte aligned activations");
+  CHECK_HIP(launch_head_bwd((const bf16raw*)dz_out.data_ptr(), (const bf16raw*)w.data_ptr(),
+                            (const bf16raw*)y_in.data_ptr(), (bf16raw*)dz_in.data_ptr(),
+                            dw.data_ptr<float>(), dbp, (int)B, (int)C, (int)H, (int)max_blocks,
+                            head_num_cus(), cur_stream()));
+  return dz_in;
 }
 
 
@@ -906,6 +979,11 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("mse_fused", &mse_fused, "mse fwd+bwd fused");
   m.def("linear_fwd", &linear_fwd, "Y = X W^T (+bias)(+relu), MFMA");
   m.def("linear_dgrad", &linear_dgrad, "dX = dZ W, MFMA");
+  m.def("linear_dgrad_relu", &linear_dgrad_relu, "dX = (dZ W) * (y_prev > 0), MFMA");
+  m.def("head_bwd_supported", &head_bwd_ok, "does the one-pass head backward serve (C, H)");
+  m.def("linear_head_bwd", &linear_head_bwd, "one-pass dz_in/dW/db of a small head on a ReLU layer",
+        py::arg("dz_out"), py::arg("w"), py::arg("y_in"), py::arg("dw"), py::arg("db"),
+        py::arg("max_blocks") = 0);
   m.def("linear_wgrad", &linear_wgrad, "dW = dZ^T X, MFMA split-K");
   m.def("linear_wgrad_into", &linear_wgrad_into, "dW accumulated into grad view");
   m.def("linear_wgrad_bias_into", &linear_wgrad_bias_into, "dW + db in one MFMA launch");

@@ -56,6 +56,9 @@
                          // a separate reduce kernel combines the slabs —
                          // guide §5 "splitk-seam": slab reducer beats an
                          // fp32-atomicAdd accumulator)
+#define EPI_BF16_MASK 6  // bf16 store, zeroed where mask[m][n] <= 0 (mask: bf16
+                         // [M][N], same layout as C) — dgrad with the upstream
+                         // ReLU backward folded in
 
 typedef shortx8 frag_t;  // 8 bf16 (4 VGPRs)
 
@@ -406,7 +409,8 @@ __global__ __launch_bounds__(WR * WC * 64, 2) void gemm_kernel(const void* __res
                                                    const float* __restrict__ bias, int M, int N,
                                                    int K, int64_t sam, int64_t sak, int64_t sbk,
                                                    int64_t sbn, int k_per_split,
-                                                   float* __restrict__ Db, int ones_row) {
+                                                   float* __restrict__ Db, int ones_row,
+                                                   const bf16raw* __restrict__ mask) {
   constexpr int BMt = WR * 64;
   constexpr int BNt = WC * 64;
   constexpr int BKT = (WC == 1) ? 32 : 64;  // narrow tile keeps BK=32 (LDS budget)
@@ -607,6 +611,14 @@ __global__ __launch_bounds__(WR * WC * 64, 2) void gemm_kernel(const void* __res
     const int oct = lane & 3;            // which 16-col half-octet pair
 #pragma unroll
     for (int mi = 0; mi < 4; ++mi) {
+      // mask octets are fetched before the fragment goes through the LDS
+      // scratch so the global load overlaps the transpose
+      shortx8 mk[2] = {};
+      if (EPI == EPI_BF16_MASK && m_base + mi * 16 + orow < M) {
+        const bf16raw* mp = mask + (int64_t)(m_base + mi * 16 + orow) * N + n_base + oct * 16;
+        mk[0] = *(const shortx8*)mp;
+        mk[1] = *(const shortx8*)(mp + 8);
+      }
 #pragma unroll
       for (int ni = 0; ni < 4; ++ni)
 #pragma unroll
@@ -626,6 +638,7 @@ __global__ __launch_bounds__(WR * WC * 64, 2) void gemm_kernel(const void* __res
             if (EPI == EPI_BIAS || EPI == EPI_BIAS_RELU) val += bias[n + j];
             if (EPI == EPI_BIAS_RELU || EPI == EPI_RELU) val = fmaxf(val, 0.f);
             outp[j] = (short)f32_to_bf16(val);
+            if (EPI == EPI_BF16_MASK && !(bf16_to_f32((bf16raw)mk[h][j]) > 0.f)) outp[j] = 0;
           }
           *(shortx8*)(Cb + (int64_t)m * N + n) = *(const shortx8*)outp;
         }
@@ -679,7 +692,9 @@ __global__ __launch_bounds__(WR * WC * 64, 2) void gemm_kernel(const void* __res
           int64_t off = (int64_t)m * N + n;
           if (EPI == EPI_BIAS || EPI == EPI_BIAS_RELU) val += bias[n];
           if (EPI == EPI_BIAS_RELU || EPI == EPI_RELU) val = fmaxf(val, 0.f);
-          Cb[off] = f32_to_bf16(val);
+          bf16raw o = f32_to_bf16(val);
+          if (EPI == EPI_BF16_MASK && !(bf16_to_f32(mask[off]) > 0.f)) o = 0;
+          Cb[off] = o;
         }
       }
     }
@@ -781,13 +796,16 @@ extern "C" hipError_t launch_wgrad_slab(const void* A, const void* B, int b_is_f
   do {                                                                                        \
     if (wide)                                                                                 \
       gemm_kernel<BF32, EPI_F32_SLAB, true, 2, 4, false><<<grid, block, 0, stream>>>(         \
-          A, B, ws, nullptr, nullptr, M, N, K, sam, sak, sbk, sbn, kps, nullptr, ones_row); \
+          A, B, ws, nullptr, nullptr, M, N, K, sam, sak, sbk, sbn, kps, nullptr, ones_row,   \
+          nullptr);                                                                         \
     else if (narrow)                                                                          \
       gemm_kernel<BF32, EPI_F32_SLAB, true, 4, 1, false><<<grid, block, 0, stream>>>(         \
-          A, B, ws, nullptr, nullptr, M, N, K, sam, sak, sbk, sbn, kps, nullptr, ones_row); \
+          A, B, ws, nullptr, nullptr, M, N, K, sam, sak, sbk, sbn, kps, nullptr, ones_row,   \
+          nullptr);                                                                         \
     else                                                                                      \
       gemm_kernel<BF32, EPI_F32_SLAB, true, 2, 2, false><<<grid, block, 0, stream>>>(         \
-          A, B, ws, nullptr, nullptr, M, N, K, sam, sak, sbk, sbn, kps, nullptr, ones_row); \
+          A, B, ws, nullptr, nullptr, M, N, K, sam, sak, sbk, sbn, kps, nullptr, ones_row,   \
+          nullptr);                                                                         \
   } while (0)
 
   if (b_is_f32)
@@ -811,10 +829,13 @@ extern "C" hipError_t launch_wgrad_slab(const void* A, const void* B, int b_is_f
   return hipSuccess;
 }
 
-extern "C" hipError_t launch_gemm_bf16(const void* A, const void* B, int b_is_f32, float* Cf,
-                                       bf16raw* Cb, const float* bias, int M, int N, int K,
-                                       int64_t sam, int64_t sak, int64_t sbk, int64_t sbn, int epi,
-                                       int splitk, float* Db, int ones_row, hipStream_t stream) {
+// mask is read only by EPI_BF16_MASK (bf16 [M][N], same layout as Cb).
+extern "C" hipError_t launch_gemm_bf16_mask(const void* A, const void* B, int b_is_f32, float* Cf,
+                                            bf16raw* Cb, const float* bias, int M, int N, int K,
+                                            int64_t sam, int64_t sak, int64_t sbk, int64_t sbn,
+                                            int epi, int splitk, float* Db, int ones_row,
+                                            const bf16raw* mask, hipStream_t stream) {
+  if (epi == EPI_BF16_MASK && mask == nullptr) return hipErrorInvalidValue;
   dim3 block(256);
   // splitk < 0 => |splitk| slices AND force the atomic (accumulate) epilogue
   // even if the recomputed slice count collapses to 1.
@@ -855,25 +876,25 @@ extern "C" hipError_t launch_gemm_bf16(const void* A, const void* B, int b_is_f3
   do {                                                                                       \
     if (wide)                                                                                \
       gemm_kernel<BF32, EPIC, SPK, 2, 4, false><<<grid, block, 0, stream>>>(                 \
-          A, B, Cf, Cb, bias, M, N, K, sam, sak, sbk, sbn, kps, Db, ones_row);               \
+          A, B, Cf, Cb, bias, M, N, K, sam, sak, sbk, sbn, kps, Db, ones_row, mask);               \
     else if (narrow && ag && bg)                                                             \
       gemm_kernel<BF32, EPIC, SPK, 4, 1, true, true><<<grid, block, 0, stream>>>(            \
-          A, B, Cf, Cb, bias, M, N, K, sam, sak, sbk, sbn, kps, Db, ones_row);               \
+          A, B, Cf, Cb, bias, M, N, K, sam, sak, sbk, sbn, kps, Db, ones_row, mask);               \
     else if (narrow && ag)                                                                   \
       gemm_kernel<BF32, EPIC, SPK, 4, 1, true><<<grid, block, 0, stream>>>(                  \
-          A, B, Cf, Cb, bias, M, N, K, sam, sak, sbk, sbn, kps, Db, ones_row);               \
+          A, B, Cf, Cb, bias, M, N, K, sam, sak, sbk, sbn, kps, Db, ones_row, mask);               \
     else if (narrow)                                                                         \
       gemm_kernel<BF32, EPIC, SPK, 4, 1, false><<<grid, block, 0, stream>>>(                 \
-          A, B, Cf, Cb, bias, M, N, K, sam, sak, sbk, sbn, kps, Db, ones_row);               \
+          A, B, Cf, Cb, bias, M, N, K, sam, sak, sbk, sbn, kps, Db, ones_row, mask);               \
     else if (ag && bg)                                                                       \
       gemm_kernel<BF32, EPIC, SPK, 2, 2, true, true><<<grid, block, 0, stream>>>(            \
-          A, B, Cf, Cb, bias, M, N, K, sam, sak, sbk, sbn, kps, Db, ones_row);               \
+          A, B, Cf, Cb, bias, M, N, K, sam, sak, sbk, sbn, kps, Db, ones_row, mask);               \
     else if (ag)                                                                             \
       gemm_kernel<BF32, EPIC, SPK, 2, 2, true><<<grid, block, 0, stream>>>(                  \
-          A, B, Cf, Cb, bias, M, N, K, sam, sak, sbk, sbn, kps, Db, ones_row);               \
+          A, B, Cf, Cb, bias, M, N, K, sam, sak, sbk, sbn, kps, Db, ones_row, mask);               \
     else                                                                                     \
       gemm_kernel<BF32, EPIC, SPK, 2, 2, false><<<grid, block, 0, stream>>>(                 \
-          A, B, Cf, Cb, bias, M, N, K, sam, sak, sbk, sbn, kps, Db, ones_row);               \
+          A, B, Cf, Cb, bias, M, N, K, sam, sak, sbk, sbn, kps, Db, ones_row, mask);               \
   } while (0)
 
   if (b_is_f32) {
@@ -883,6 +904,7 @@ extern "C" hipError_t launch_gemm_bf16(const void* A, const void* B, int b_is_f3
     else if (epi == EPI_BIAS) DISPATCH(true, EPI_BIAS, false);
     else if (epi == EPI_BIAS_RELU) DISPATCH(true, EPI_BIAS_RELU, false);
     else if (epi == EPI_RELU) DISPATCH(true, EPI_RELU, false);
+    else if (epi == EPI_BF16_MASK) DISPATCH(true, EPI_BF16_MASK, false);
     else return hipErrorInvalidValue;
   } else {
     if (atomic && epi == EPI_F32) DISPATCH(false, EPI_F32, true);
@@ -891,9 +913,18 @@ extern "C" hipError_t launch_gemm_bf16(const void* A, const void* B, int b_is_f3
     else if (epi == EPI_BIAS) DISPATCH(false, EPI_BIAS, false);
     else if (epi == EPI_BIAS_RELU) DISPATCH(false, EPI_BIAS_RELU, false);
     else if (epi == EPI_RELU) DISPATCH(false, EPI_RELU, false);
+    else if (epi == EPI_BF16_MASK) DISPATCH(false, EPI_BF16_MASK, false);
     else return hipErrorInvalidValue;
   }
 #undef DISPATCH
   HIP_CHECK_LAUNCH();
   return hipSuccess;
+}
+
+extern "C" hipError_t launch_gemm_bf16(const void* A, const void* B, int b_is_f32, float* Cf,
+                                       bf16raw* Cb, const float* bias, int M, int N, int K,
+                                       int64_t sam, int64_t sak, int64_t sbk, int64_t sbn, int epi,
+                                       int splitk, float* Db, int ones_row, hipStream_t stream) {
+  return launch_gemm_bf16_mask(A, B, b_is_f32, Cf, Cb, bias, M, N, K, sam, sak, sbk, sbn, epi,
+                               splitk, Db, ones_row, nullptr, stream);
 }

@@ -1,0 +1,258 @@
+// One-pass backward of a small classifier head (C <= 16 classes) that sits
+// on a ReLU layer:  logits = y_in @ w^T,  y_in = relu(...)  [B, H] bf16.
+//
+//   dz_in = (dz_out @ w) * (y_in > 0)     bf16 [B, H]
+//   dw   += dz_out^T @ y_in               fp32 [C, H]
+//   db   += colsum(dz_out)                fp32 [C]
+//
+// The three-kernel route (wgrad GEMM with 10 live rows in a 128-row MFMA
+// tile, K=10 dgrad GEMM, relu_bwd) reads y_in twice and writes + re-reads the
+// unmasked dgrad; here y_in is read once and dz_in written once.
+//
+// Persistent blocks stride over ROWS-row tiles of y_in.  A tile is staged by
+// async global->LDS DMA (double-buffered: tile t+1 is in flight while tile t
+// is consumed; one barrier per tile) into a pad-free row-major image whose
+// 16 B slots are XOR-swizzled by row.  The image is used twice:
+//   * dgrad computes dz_in^T = w^T[H,C] x dz_out^T[C,rows] so a lane's
+//     accumulators are consecutive h of ONE row; two MFMAs whose M-rows are
+//     interleaved in groups of four give each lane 8 consecutive h = one
+//     16 B store, and the mask is the matching 16 B of the y_in image.
+//   * wgrad computes dW^T[H,16] += y_in^T x dz_out over the tile rows.  The
+//     k-packed fragments of the row-major image come from the transposing
+//     LDS read (ds_read_b64_tr_b16; lane semantics in
+//     profiles/bench_resnet18_optimization_log.md, "TR-mode wgrad"): every
+//     lane of a 16-lane quarter passes the address of 4 consecutive columns
+//     of one row and receives one column of the quarter's 4x16 block.
+// dz_out's tile is tiny: it is staged through registers into a [rows][16]
+// image with the class dimension zero-padded, read plainly (k-contiguous)
+// by the dgrad and through the same transposing read by the wgrad.  Each
+// wave owns 32-column groups of H for both products; w fragments and the
+// dW/db accumulators stay in registers across all of a block's tiles and
+// are flushed once with fp32 atomicAdd.
+
+#include "common.h"
+
+typedef shortx8 hfrag_t;  // 8 bf16 (4 VGPRs)
+
+#define HEAD_THREADS 256
+#define HEAD_CPAD 16  // class dim padded to 16 in the dz_out image
+
+__host__ __device__ constexpr int head_rows(int H) { return H <= 256 ? 64 : 32; }
+
+template <bool TR>
+__device__ __forceinline__ hfrag_t head_tr_frag(const bf16raw* __restrict__ img, int stride,
+                                                int xm, int rb, int q, int l15, int col0) {
+  // fragment value i <-> tile row rb + (i/4)*16 + q*4 + (i%4), column
+  // col0 + l15; the same row order is used for both MFMA operands
+  hfrag_t f;
+  if (TR) {
+    const int col = col0 + 4 * (l15 & 3);
+#pragma unroll
+    for (int jh = 0; jh < 2; ++jh) {
+      const int row = rb + jh * 16 + q * 4 + (l15 >> 2);
+      const bf16raw* p = img + row * stride + ((((col >> 3) ^ (row & xm)) << 3) | (col & 7));
+      shortx4 v = __builtin_amdgcn_ds_read_tr16_b64_v4i16(
+          (__attribute__((address_space(3))) shortx4*)p);
+#pragma unroll
+      for (int j = 0; j < 4; ++j) f[jh * 4 + j] = v[j];
+    }
+  } else {
+    const int col = col0 + l15;
+#pragma unroll
+    for (int i = 0; i < 8; ++i) {
+      const int row = rb + (i >> 2) * 16 + q * 4 + (i & 3);
+      f[i] = (short)img[row * stride + ((((col >> 3) ^ (row & xm)) << 3) | (col & 7))];
+    }
+  }
+  return f;
+}
+
+template <int H, bool TR>
+__global__ __launch_bounds__(HEAD_THREADS, 2) void head_bwd_kernel(
+    const bf16raw* __restrict__ dz_out, const bf16raw* __restrict__ w,
+    const bf16raw* __restrict__ y_in, bf16raw* __restrict__ dz_in, float* __restrict__ dw,
+    float* __restrict__ db, int B, int C) {
+  constexpr int ROWS = head_rows(H);
+  constexpr int SLOTS = H / 8;                     // 16 B slots per image row
+  constexpr int XM = (SLOTS % 16 == 0) ? 15 : 7;   // slot ^= row & XM
+  constexpr int NP = H / 32;                       // 32-column groups
+  constexpr int PW = (NP + 3) / 4;                 // groups per wave
+  constexpr int NCH = ROWS * H * 2 / 1024;         // 1 KB DMA chunks per tile
+  constexpr int EPT = ROWS * HEAD_CPAD / HEAD_THREADS;  // dz elements per thread
+  static_assert(H % 64 == 0 && H <= 512, "unsupported H");
+
+  __shared__ __attribute__((aligned(16))) bf16raw ys[2][ROWS * H];
+  __shared__ __attribute__((aligned(16))) bf16raw dzs[2][ROWS * HEAD_CPAD];
+
+  const int t = threadIdx.x;
+  const int wid = t >> 6, lane = t & 63;
+  const int l15 = lane & 15, q = lane >> 4;
+  const int ntiles = (B + ROWS - 1) / ROWS;
+
+  // w fragments (dgrad A operand, M = h, K = class padded to 32).  M-row m of
+  // fragment e of a group maps to h = group*32 + (m/4)*8 + e*4 + (m%4).
+  hfrag_t wf[PW][2];
+#pragma unroll
+  for (int pi = 0; pi < PW; ++pi) {
+    const int p = wid + pi * 4;
+#pragma unroll
+    for (int e = 0; e < 2; ++e) {
+      const int h = p * 32 + (l15 >> 2) * 8 + e * 4 + (l15 & 3);
+#pragma unroll
+      for (int i = 0; i < 8; ++i) {
+        const int c = q * 8 + i;
+        wf[pi][e][i] = (p < NP && c < C) ? (short)w[c * H + h] : (short)0;
+      }
+    }
+  }
+  hfrag_t ones;
+#pragma unroll
+  for (int i = 0; i < 8; ++i) ones[i] = (short)0x3F80;
+
+  floatx4 accw[PW][2] = {};
+  floatx4 accb = {0.f, 0.f, 0.f, 0.f};
+
+  // dz_out tile -> registers (class dim zero-padded, rows past B zero)
+  const int zrow = (t * EPT) / HEAD_CPAD, zc0 = (t * EPT) % HEAD_CPAD;
+  bf16raw zr[EPT];
+  auto load_dz = [&](int tile) {
+    const int64_t gr = (int64_t)tile * ROWS + zrow;
+#pragma unroll
+    for (int j = 0; j < EPT; ++j)
+      zr[j] = (gr < B && zc0 + j < C) ? dz_out[gr * C + zc0 + j] : (bf16raw)0;
+  };
+  auto write_dz = [&](int b) {
+#pragma unroll
+    for (int j = 0; j < EPT; ++j) dzs[b][zrow * HEAD_CPAD + zc0 + j] = zr[j];
+  };
+  // y_in tile -> LDS by DMA; rows past B re-read row B-1 (their dz rows are
+  // zero and their outputs are not stored)
+  auto dma_y = [&](int b, int tile) {
+#pragma unroll
+    for (int c = wid; c < NCH; c += 4) {
+      const int o = c * 1024 + lane * 16;
+      const int row = o / (H * 2);
+      const int slot = ((o % (H * 2)) >> 4) ^ (row & XM);
+      int64_t gr = (int64_t)tile * ROWS + row;
+      if (gr > B - 1) gr = B - 1;
+      const bf16raw* g = y_in + gr * H + slot * 8;
+      __builtin_amdgcn_global_load_lds(
+          (const __attribute__((address_space(1))) unsigned int*)g,
+          (__attribute__((address_space(3))) unsigned int*)(ys[b] + c * 512), 16, 0, 0);
+    }
+  };
+
+  int tile = blockIdx.x;
+  int buf = 0;
+  if (tile < ntiles) {
+    dma_y(0, tile);
+    load_dz(tile);
+    write_dz(0);
+  }
+  for (; tile < ntiles; tile += gridDim.x) {
+    // tile's images are complete and every wave is done with the other pair
+    __syncthreads();
+    const int next = tile + gridDim.x;
+    if (next < ntiles) {
+      load_dz(next);
+      dma_y(buf ^ 1, next);
+    }
+    const bf16raw* yb = ys[buf];
+    const bf16raw* zb = dzs[buf];
+    const int64_t row0 = (int64_t)tile * ROWS;
+
+    // ---- dgrad + mask ----
+#pragma unroll
+    for (int rf = 0; rf < ROWS / 16; ++rf) {
+      const int row = rf * 16 + l15;
+      hfrag_t bz = {};
+      if (q < 2) bz = *(const hfrag_t*)&zb[row * HEAD_CPAD + q * 8];
+#pragma unroll
+      for (int pi = 0; pi < PW; ++pi) {
+        const int p = wid + pi * 4;
+        if (p < NP) {
+          floatx4 z = {0.f, 0.f, 0.f, 0.f};
+          floatx4 a0 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wf[pi][0], bz, z, 0, 0, 0);
+          floatx4 a1 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wf[pi][1], bz, z, 0, 0, 0);
+          const int slot = p * 4 + q;
+          const shortx8 mk = *(const shortx8*)&yb[row * H + ((slot ^ (row & XM)) << 3)];
+          shortx8 out;
+#pragma unroll
+          for (int j = 0; j < 4; ++j) {
+            out[j] = bf16_to_f32((bf16raw)mk[j]) > 0.f ? (short)f32_to_bf16(a0[j]) : (short)0;
+            out[4 + j] =
+                bf16_to_f32((bf16raw)mk[4 + j]) > 0.f ? (short)f32_to_bf16(a1[j]) : (short)0;
+          }
+          if (row0 + row < B) *(shortx8*)(dz_in + (row0 + row) * H + slot * 8) = out;
+        }
+      }
+    }
+
+    // ---- wgrad + bias grad ----
+#pragma unroll
+    for (int ks = 0; ks < ROWS / 32; ++ks) {
+      const hfrag_t bz = head_tr_frag<TR>(zb, HEAD_CPAD, 0, ks * 32, q, l15, 0);
+      if (wid == 0)
+        accb = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ones, bz, accb, 0, 0, 0);
+#pragma unroll
+      for (int pi = 0; pi < PW; ++pi) {
+        const int p = wid + pi * 4;
+        if (p < NP) {
+#pragma unroll
+          for (int e = 0; e < 2; ++e) {
+            const hfrag_t ay = head_tr_frag<TR>(yb, H, XM, ks * 32, q, l15, p * 32 + e * 16);
+            accw[pi][e] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ay, bz, accw[pi][e], 0, 0, 0);
+          }
+        }
+      }
+    }
+
+    if (next < ntiles) write_dz(buf ^ 1);
+    buf ^= 1;
+  }
+
+  // flush: accumulator lane (c = l15, q), element r <-> h = base + 4q + r
+  if (l15 < C) {
+#pragma unroll
+    for (int pi = 0; pi < PW; ++pi) {
+      const int p = wid + pi * 4;
+      if (p < NP) {
+#pragma unroll
+        for (int e = 0; e < 2; ++e)
+#pragma unroll
+          for (int r = 0; r < 4; ++r)
+            atomicAdd(dw + l15 * H + p * 32 + e * 16 + q * 4 + r, accw[pi][e][r]);
+      }
+    }
+    if (db != nullptr && wid == 0 && q == 0) atomicAdd(db + l15, accb[0]);
+  }
+}
+
+// 1 when (C, H) is served by the fused kernel
+extern "C" int head_bwd_supported(int C, int H) {
+  return C >= 1 && C <= HEAD_CPAD && (H == 64 || H == 128 || H == 256 || H == 512);
+}
+
+// max_blocks > 0 caps the grid (tests force several tiles per block with it)
+extern "C" hipError_t launch_head_bwd(const bf16raw* dz_out, const bf16raw* w,
+                                      const bf16raw* y_in, bf16raw* dz_in, float* dw, float* db,
+                                      int B, int C, int H, int max_blocks, int num_cus,
+                                      hipStream_t stream) {
+  if (!head_bwd_supported(C, H) || B < 1) return hipErrorInvalidValue;
+  const int ntiles = (B + head_rows(H) - 1) / head_rows(H);
+  int grid = 2 * (num_cus > 0 ? num_cus : 256);
+  if (max_blocks > 0 && grid > max_blocks) grid = max_blocks;
+  if (grid > ntiles) grid = ntiles;
+#define HEAD_LAUNCH(HH)                                                                     \
+  head_bwd_kernel<HH, true><<<dim3(grid), dim3(HEAD_THREADS), 0, stream>>>(dz_out, w, y_in, \
+                                                                            dz_in, dw, db, B, C)
+  switch (H) {
+    case 64: HEAD_LAUNCH(64); break;
+    case 128: HEAD_LAUNCH(128); break;
+    case 256: HEAD_LAUNCH(256); break;
+    default: HEAD_LAUNCH(512); break;
+  }
+#undef HEAD_LAUNCH
+  HIP_CHECK_LAUNCH();
+  return hipSuccess;
+}

@@ -7,6 +7,8 @@ backward:
   dx = dz @ W                  — MFMA
   dW = dz^T @ x                — MFMA, split-K over batch (atomic fp32)
   db = colsum(dz)              — bias_grad
+Layer stacks (hip_mlp_chain) fold the ReLU mask into the consumer's dgrad
+epilogue and run a small classifier head's whole backward in one pass.
 
 The CPU fallback keeps identical semantics so the same model code runs in the
 no-GPU sandbox; on a GPU the extension is REQUIRED (ops.ext() raises).
@@ -30,6 +32,48 @@ def _choose_splitk(batch: int, n_out: int, k_in: int) -> int:
     want = max(1, 2048 // max(1, base))
     max_by_rows = max(1, batch // 512)
     return int(min(want, max_by_rows, 512))
+
+
+def _linear_param_grads(ext, dz, x, w, b, need_w: bool, need_b: bool):
+    """dW / db of one linear layer from its pre-activation gradient ``dz`` and
+    saved input ``x``.  Returns (dw, db) for autograd to accumulate, or None
+    for a gradient that went down the direct path.
+
+    Direct-grad path: when FlatBuckets installed this param, its .grad is a
+    pre-zeroed flat-bucket view — accumulate straight into it (no fresh
+    alloc, no autograd add pass) and notify the bucket so the overlapped
+    all-reduce launches; autograd sees None."""
+    dw = db = None
+    has_bias = b is not None
+    w_notify = getattr(w, "_bucket_notify", None)
+    b_notify = getattr(b, "_bucket_notify", None) if has_bias else None
+    sk = _choose_splitk(dz.shape[0], w.shape[0], w.shape[1])
+    w_direct = w_notify is not None and w.grad is not None
+    b_direct = b_notify is not None and has_bias and b.grad is not None
+
+    # NB: the fused dW+db ones column can push N across a tile boundary
+    # (fc2: 257 -> an extra 99.6%-dead N-tile); splitting into wgrad +
+    # bias_grad was measured NEUTRAL end-to-end (the separate column-sum
+    # pass costs what the dead tile does) — keep the single fused launch.
+    if need_w and w_direct and has_bias and b_direct:
+        # dW and db in ONE MFMA launch (virtual ones column)
+        ext.linear_wgrad_bias_into(dz, x, w.grad, b.grad, sk)
+        w_notify()
+        b_notify()
+    else:
+        if need_w:
+            if w_direct:
+                ext.linear_wgrad_into(dz, x, w.grad, sk)
+                w_notify()
+            else:
+                dw = ext.linear_wgrad(dz, x, sk)
+        if has_bias and need_b:
+            if b_direct:
+                ext.bias_grad_into(dz, b.grad)
+                b_notify()
+            else:
+                db = ext.bias_grad(dz)
+    return dw, db
 
 
 class _LinearFn(torch.autograd.Function):
@@ -59,40 +103,8 @@ class _LinearFn(torch.autograd.Function):
         dz = ext.relu_bwd(dy, y) if ctx.relu else dy
         dx = ext.linear_dgrad(dz, wb) if ctx.needs_input_grad[0] else None
 
-        # Direct-grad path: when FlatBuckets installed this param, its .grad
-        # is a pre-zeroed flat-bucket view — accumulate straight into it (no
-        # fresh alloc, no autograd add pass) and notify the bucket so the
-        # overlapped all-reduce launches; autograd sees None.
-        dw = db = None
-        b = ctx.bias_ref
-        w_notify = getattr(w, "_bucket_notify", None)
-        b_notify = getattr(b, "_bucket_notify", None) if b is not None else None
-        sk = _choose_splitk(dz.shape[0], w.shape[0], w.shape[1])
-        w_direct = w_notify is not None and w.grad is not None
-        b_direct = b_notify is not None and b is not None and b.grad is not None
-
-        # NB: the fused dW+db ones column can push N across a tile boundary
-        # (fc2: 257 -> an extra 99.6%-dead N-tile); splitting into wgrad +
-        # bias_grad was measured NEUTRAL end-to-end (the separate column-sum
-        # pass costs what the dead tile does) — keep the single fused launch.
-        if ctx.needs_input_grad[1] and w_direct and ctx.has_bias and b_direct:
-            # dW and db in ONE MFMA launch (virtual ones column)
-            ext.linear_wgrad_bias_into(dz, x, w.grad, b.grad, sk)
-            w_notify()
-            b_notify()
-        else:
-            if ctx.needs_input_grad[1]:
-                if w_direct:
-                    ext.linear_wgrad_into(dz, x, w.grad, sk)
-                    w_notify()
-                else:
-                    dw = ext.linear_wgrad(dz, x, sk)
-            if ctx.has_bias and ctx.needs_input_grad[2]:
-                if b_direct:
-                    ext.bias_grad_into(dz, b.grad)
-                    b_notify()
-                else:
-                    db = ext.bias_grad(dz)
+        dw, db = _linear_param_grads(ext, dz, x, w, ctx.bias_ref, ctx.needs_input_grad[1],
+                                     ctx.has_bias and ctx.needs_input_grad[2])
         return dx, dw, db, None
 
 
@@ -118,6 +130,137 @@ def hip_linear(
         return y
     y = F.linear(x, weight, bias)
     return F.relu(y) if relu else y
+
+
+# Tests flip this to force the per-layer route for the classifier head.
+_HEAD_FUSION = True
+
+
+def _head_bwd_ok(ext, w: torch.Tensor) -> bool:
+    return (_HEAD_FUSION and w.dtype == torch.bfloat16
+            and ext.head_bwd_supported(w.shape[0], w.shape[1]))
+
+
+def linear_head_bwd(dz_out, w, y_in, dw, db=None, max_blocks: int = 0):
+    """Backward of a bias-only (no activation) head ``y_in @ w^T`` whose input
+    ``y_in`` is a ReLU output: returns ``dz_in = (dz_out @ w) * (y_in > 0)``
+    and accumulates ``dw += dz_out^T @ y_in``, ``db += colsum(dz_out)`` (fp32,
+    caller zeroes).  One pass over ``y_in`` (head_bwd.hip) where the shape
+    qualifies, else the three-kernel route."""
+    ext = ops.ext()
+    if _head_bwd_ok(ext, w):
+        return ext.linear_head_bwd(dz_out, w, y_in, dw, db, max_blocks)
+    sk = _choose_splitk(dz_out.shape[0], w.shape[0], w.shape[1])
+    if db is not None:
+        ext.linear_wgrad_bias_into(dz_out, y_in, dw, db, sk)
+    else:
+        ext.linear_wgrad_into(dz_out, y_in, dw, sk)
+    return ext.relu_bwd(ext.linear_dgrad(dz_out, w), y_in)
+
+
+class _MLPChainFn(torch.autograd.Function):
+    """A stack of linear(+bias)(+relu) layers as ONE autograd node.  Forward
+    is the per-layer kernel sequence of _LinearFn.  Backward knows each
+    layer's producer, so the producer's ReLU mask is applied where the dgrad
+    tile is still in registers (linear_dgrad_relu) instead of in a separate
+    relu_bwd pass, and a small classifier head on a ReLU layer gets its
+    dgrad, mask, dW and db from one pass (linear_head_bwd)."""
+
+    @staticmethod
+    def forward(ctx, x, relus, *params):
+        ext = ops.ext()
+        n = len(relus)
+        saved = [x]
+        biases = []
+        h = x
+        for i in range(n):
+            w, b = params[2 * i], params[2 * i + 1]
+            wb = ext.cast_f32_bf16(w) if w.dtype == torch.float32 else w
+            h = ext.linear_fwd(h, wb, b, relus[i])
+            saved += [w, wb, h]
+            biases.append(b)
+        ctx.save_for_backward(*saved)
+        ctx.relus = tuple(relus)
+        ctx.bias_refs = biases
+        return h
+
+    @staticmethod
+    def backward(ctx, dy):
+        ext = ops.ext()
+        saved = ctx.saved_tensors
+        relus = ctx.relus
+        n = len(relus)
+        x0 = saved[0]
+        ws = [saved[1 + 3 * i] for i in range(n)]
+        wbs = [saved[2 + 3 * i] for i in range(n)]
+        ys = [saved[3 + 3 * i] for i in range(n)]
+        dy = dy.contiguous()
+        if dy.dtype != torch.bfloat16:
+            dy = dy.to(torch.bfloat16)
+        grads = [None] * (2 * n)
+        dz = ext.relu_bwd(dy, ys[n - 1]) if relus[n - 1] else dy
+        for i in range(n - 1, -1, -1):
+            w, wb, b = ws[i], wbs[i], ctx.bias_refs[i]
+            xin = ys[i - 1] if i > 0 else x0
+            need_w = ctx.needs_input_grad[2 + 2 * i]
+            need_b = b is not None and ctx.needs_input_grad[3 + 2 * i]
+            masked = i > 0 and relus[i - 1]
+            if i == n - 1 and masked and not relus[i] and need_w and _head_bwd_ok(ext, wb):
+                dz, grads[2 * i], grads[2 * i + 1] = _MLPChainFn._head(ext, dz, xin, w, wb, b,
+                                                                      need_b)
+                continue
+            dz_prev = None
+            if masked:
+                dz_prev = ext.linear_dgrad_relu(dz, wb, xin)
+            elif i > 0 or ctx.needs_input_grad[0]:
+                dz_prev = ext.linear_dgrad(dz, wb)
+            grads[2 * i], grads[2 * i + 1] = _linear_param_grads(ext, dz, xin, w, b, need_w,
+                                                                 need_b)
+            dz = dz_prev
+        return (dz, None, *grads)
+
+    @staticmethod
+    def _head(ext, dz, xin, w, wb, b, need_b):
+        """One-pass head backward with _linear_param_grads' gradient rules:
+        direct into the bucket views (+ notify) where installed, else fresh
+        zeroed tensors handed to autograd."""
+        w_notify = getattr(w, "_bucket_notify", None)
+        b_notify = getattr(b, "_bucket_notify", None) if b is not None else None
+        w_direct = w_notify is not None and w.grad is not None
+        b_direct = need_b and b_notify is not None and b.grad is not None
+        dw_t = w.grad if w_direct else torch.zeros_like(w, dtype=torch.float32)
+        db_t = None
+        if need_b:
+            db_t = b.grad if b_direct else torch.zeros_like(b, dtype=torch.float32)
+        dz_prev = ext.linear_head_bwd(dz, wb, xin, dw_t, db_t, 0)
+        if w_direct:
+            w_notify()
+        if b_direct:
+            b_notify()
+        return dz_prev, (None if w_direct else dw_t), (None if b_direct else db_t)
+
+
+def hip_mlp_chain(x: torch.Tensor, layers) -> torch.Tensor:
+    """Run ``layers`` = [(weight, bias, relu), ...] as a chain of fused
+    linear(+bias)(+relu) layers.  GPU: one autograd node (_MLPChainFn) so the
+    backward can fuse across layer boundaries; CPU: F.linear / F.relu."""
+    if x.is_cuda:
+        if x.dtype != torch.bfloat16:
+            x = x.to(torch.bfloat16)
+        if not x.is_contiguous():
+            x = x.contiguous()
+        lead = x.shape[:-1]
+        flat = []
+        for w, b, _ in layers:
+            flat += [w, b]
+        relus = tuple(bool(r) for _, _, r in layers)
+        y = _MLPChainFn.apply(x.reshape(-1, x.shape[-1]), relus, *flat)
+        return y.view(*lead, y.shape[-1]) if x.dim() != 2 else y
+    for w, b, relu in layers:
+        x = F.linear(x, w, b)
+        if relu:
+            x = F.relu(x)
+    return x
 
 
 class _Conv2dFn(torch.autograd.Function):

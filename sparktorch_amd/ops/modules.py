@@ -28,6 +28,7 @@ from sparktorch_amd.ops.functional import (
     hip_linear,
     hip_max_pool2d,
     hip_max_pool2d_nhwc,
+    hip_mlp_chain,
     hip_relu,
     hip_mse,
 )
@@ -321,9 +322,10 @@ class MnistMLPFused(nn.Module):
         self.fc3 = HipLinear(hidden, classes, activation=None)
 
     def forward(self, x: torch.Tensor) -> torch.Tensor:
-        if x.is_cuda and x.dtype != torch.bfloat16:
-            x = x.to(torch.bfloat16)
-        return self.fc3(self.fc2(self.fc1(x)))
+        # one autograd node for the stack: the backward fuses the ReLU masks
+        # into the dgrad epilogues and the fc3 backward into one pass
+        return hip_mlp_chain(x, [(fc.weight, fc.bias, fc.activation == "relu")
+                                 for fc in (self.fc1, self.fc2, self.fc3)])
 
 
 def convert_model_for_mi355x(model: nn.Module) -> nn.Module:

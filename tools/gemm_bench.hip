@@ -27,7 +27,7 @@ double run_fwd(const bf16raw* A, const bf16raw* B, bf16raw* C, int M, int N, int
   auto launch = [&]() {
     gemm_kernel<false, EPI_BF16, false, WR, WC, AG><<<grid, 256>>>(
         A, B, nullptr, C, nullptr, M, N, K, /*sam*/ K, /*sak*/ 1, /*sbk*/ 1, /*sbn*/ K, K,
-        nullptr, -1);
+        nullptr, -1, nullptr);
   };
   launch();
   CK(hipDeviceSynchronize());
