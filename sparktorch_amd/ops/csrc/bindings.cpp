@@ -46,6 +46,10 @@ hipError_t launch_gemm_bf16_mask(const void*, const void*, int, float*, bf16raw*
                                  int, int, int, int64_t, int64_t, int64_t, int64_t, int, int,
                                  float*, int, const bf16raw*, hipStream_t);
 int head_bwd_supported(int, int);
+int linear_wgrad_stream_supported(int, int, int64_t);
+int linear_wgrad_stream_can_run(int, int, int64_t);
+hipError_t launch_linear_wgrad_stream(const bf16raw*, const bf16raw*, float*, float*, int64_t, int,
+                                      int, int, int, hipStream_t);
 hipError_t launch_head_bwd(const bf16raw*, const bf16raw*, const bf16raw*, bf16raw*, float*,
                            float*, int, int, int, int, int, hipStream_t);
 hipError_t launch_bn_stats(const bf16raw*, float*, float*, float*, float*, float*, float*, int,
@@ -487,6 +491,41 @@ void linear_wgrad_bias_into(at::Tensor dz, at::Tensor x, at::Tensor dw, at::Tens
   CHECK_HIP(launch_gemm_bf16(dz.data_ptr(), x.data_ptr(), 0, dw.data_ptr<float>(), nullptr,
                              nullptr, (int)N, (int)(K + 1), (int)B, 1, N, K, 1, 0, -(int)splitk,
                              db.data_ptr<float>(), (int)K, cur_stream()));
+}
+
+// Batch-streaming dW (+ db) for big-batch Linear layers (linear_wgrad.hip);
+// same contract as linear_wgrad_into / linear_wgrad_bias_into: the caller
+// zeroes, a second call adds.  linear_wgrad_stream_ok is the routing rule
+// (shape set and measured batch threshold); the launcher itself serves every
+// batch that linear_wgrad_stream_runs accepts.
+bool linear_wgrad_stream_runs(int64_t No, int64_t Ki, int64_t B) {
+  return No <= 256 && Ki < (1 << 24) && linear_wgrad_stream_can_run((int)No, (int)Ki, B) != 0;
+}
+bool linear_wgrad_stream_ok(int64_t No, int64_t Ki, int64_t B) {
+  return No <= 256 && Ki < (1 << 24) && linear_wgrad_stream_supported((int)No, (int)Ki, B) != 0;
+}
+
+void linear_wgrad_stream(at::Tensor dz, at::Tensor x, at::Tensor dw, c10::optional<at::Tensor> db,
+                         int64_t max_blocks) {
+  check_gpu_contig(dz, at::kBFloat16, "dz");
+  check_gpu_contig(x, at::kBFloat16, "x");
+  check_gpu_contig(dw, at::kFloat, "dw");
+  TORCH_CHECK(dz.dim() == 2 && x.dim() == 2);
+  int64_t B = dz.size(0), N = dz.size(1), K = x.size(1);
+  TORCH_CHECK(x.size(0) == B && dw.size(0) == N && dw.size(1) == K, "shape mismatch");
+  float* dbp = nullptr;
+  if (db.has_value()) {
+    check_gpu_contig(*db, at::kFloat, "db");
+    TORCH_CHECK(db->numel() == N);
+    dbp = db->data_ptr<float>();
+  }
+  TORCH_CHECK(linear_wgrad_stream_runs(N, K, B),
+              "linear_wgrad_stream: unsupported (No, Ki, B); use linear_wgrad_into");
+  TORCH_CHECK(((uintptr_t)dz.data_ptr() & 15) == 0 && ((uintptr_t)x.data_ptr() & 15) == 0,
+              "linear_wgrad_stream wants 16-byte aligned dz and x");
+  CHECK_HIP(launch_linear_wgrad_stream((const bf16raw*)dz.data_ptr(), (const bf16raw*)x.data_ptr(),
+                                       dw.data_ptr<float>(), dbp, B, (int)N, (int)K,
+                                       (int)max_blocks, head_num_cus(), cur_stream()));
 }
 
 void bias_grad_into(at::Tensor dz, at::Tensor db) {
@@ -984,6 +1023,13 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("linear_head_bwd", &linear_head_bwd, "one-pass dz_in/dW/db of a small head on a ReLU layer",
         py::arg("dz_out"), py::arg("w"), py::arg("y_in"), py::arg("dw"), py::arg("db"),
         py::arg("max_blocks") = 0);
+  m.def("linear_wgrad_stream_supported", &linear_wgrad_stream_ok,
+        "is (No, Ki) at batch B routed to the batch-streaming wgrad");
+  m.def("linear_wgrad_stream_can_run", &linear_wgrad_stream_runs,
+        "can the batch-streaming wgrad compute (No, Ki, B) at all");
+  m.def("linear_wgrad_stream", &linear_wgrad_stream,
+        "dW (+ db) accumulated by the persistent batch-streaming kernel", py::arg("dz"),
+        py::arg("x"), py::arg("dw"), py::arg("db") = py::none(), py::arg("max_blocks") = 0);
   m.def("linear_wgrad", &linear_wgrad, "dW = dZ^T X, MFMA split-K");
   m.def("linear_wgrad_into", &linear_wgrad_into, "dW accumulated into grad view");
   m.def("linear_wgrad_bias_into", &linear_wgrad_bias_into, "dW + db in one MFMA launch");

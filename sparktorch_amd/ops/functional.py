@@ -5,7 +5,8 @@ Forward math (bf16 activations, fp32 master weights, fp32 MFMA accumulate):
 backward:
   dz = dy * (y > 0)            — relu_bwd (elementwise.hip)
   dx = dz @ W                  — MFMA
-  dW = dz^T @ x                — MFMA, split-K over batch (atomic fp32)
+  dW = dz^T @ x                — MFMA, split-K over batch (atomic fp32); big
+                                 batches: persistent streaming kernel with db
   db = colsum(dz)              — bias_grad
 Layer stacks (hip_mlp_chain) fold the ReLU mask into the consumer's dgrad
 epilogue and run a small classifier head's whole backward in one pass.
@@ -34,6 +35,38 @@ def _choose_splitk(batch: int, n_out: int, k_in: int) -> int:
     return int(min(want, max_by_rows, 512))
 
 
+# Tests flip this to force the split-K gemm_kernel route for every wgrad.
+_WGRAD_STREAM = True
+# None: the kernel's measured batch threshold.  Tests lower it to drive small
+# batches through the streaming kernel.
+_WGRAD_STREAM_MIN_BATCH = None
+
+
+def _wgrad_stream_ok(ext, dz: torch.Tensor, x: torch.Tensor) -> bool:
+    if not _WGRAD_STREAM or dz.data_ptr() % 16 or x.data_ptr() % 16:
+        return False
+    B, n_out, k_in = dz.shape[0], dz.shape[1], x.shape[1]
+    if _WGRAD_STREAM_MIN_BATCH is None:
+        return ext.linear_wgrad_stream_supported(n_out, k_in, B)
+    return B >= _WGRAD_STREAM_MIN_BATCH and ext.linear_wgrad_stream_can_run(n_out, k_in, B)
+
+
+def linear_wgrad_into(dz, x, dw, db=None):
+    """``dw += dz^T @ x`` and, with ``db``, ``db += colsum(dz)`` (fp32, the
+    caller zeroes).  Big batches of a 64/128/256-output layer stream through
+    the persistent kernel (linear_wgrad.hip); everything else takes the
+    split-K gemm_kernel route."""
+    ext = ops.ext()
+    if _wgrad_stream_ok(ext, dz, x):
+        ext.linear_wgrad_stream(dz, x, dw, db, 0)
+        return
+    sk = _choose_splitk(dz.shape[0], dz.shape[1], x.shape[1])
+    if db is not None:
+        ext.linear_wgrad_bias_into(dz, x, dw, db, sk)
+    else:
+        ext.linear_wgrad_into(dz, x, dw, sk)
+
+
 def _linear_param_grads(ext, dz, x, w, b, need_w: bool, need_b: bool):
     """dW / db of one linear layer from its pre-activation gradient ``dz`` and
     saved input ``x``.  Returns (dw, db) for autograd to accumulate, or None
@@ -56,14 +89,14 @@ def _linear_param_grads(ext, dz, x, w, b, need_w: bool, need_b: bool):
     # bias_grad was measured NEUTRAL end-to-end (the separate column-sum
     # pass costs what the dead tile does) — keep the single fused launch.
     if need_w and w_direct and has_bias and b_direct:
-        # dW and db in ONE MFMA launch (virtual ones column)
-        ext.linear_wgrad_bias_into(dz, x, w.grad, b.grad, sk)
+        # dW and db in ONE launch (streaming kernel, else virtual ones column)
+        linear_wgrad_into(dz, x, w.grad, b.grad)
         w_notify()
         b_notify()
     else:
         if need_w:
             if w_direct:
-                ext.linear_wgrad_into(dz, x, w.grad, sk)
+                linear_wgrad_into(dz, x, w.grad)
                 w_notify()
             else:
                 dw = ext.linear_wgrad(dz, x, sk)
