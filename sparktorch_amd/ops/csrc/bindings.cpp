@@ -50,6 +50,8 @@ int linear_wgrad_stream_supported(int, int, int64_t);
 int linear_wgrad_stream_can_run(int, int, int64_t);
 hipError_t launch_linear_wgrad_stream(const bf16raw*, const bf16raw*, float*, float*, int64_t, int,
                                       int, int, int, hipStream_t);
+hipError_t launch_sample_gather(const void*, int, const void*, int, void*, void*, int*, const int*,
+                                uint32_t, int64_t, int, int, int, int, hipStream_t);
 hipError_t launch_head_bwd(const bf16raw*, const bf16raw*, const bf16raw*, bf16raw*, float*,
                            float*, int, int, int, int, int, hipStream_t);
 hipError_t launch_bn_stats(const bf16raw*, float*, float*, float*, float*, float*, float*, int,
@@ -387,6 +389,55 @@ static int head_num_cus() {
     cus[dev] = n;
   }
   return cus[dev];
+}
+
+// Draw minibatch `*step_dev` under `seed` and gather its rows (sample_gather.hip):
+// xb[j] = x[idx[j]], yb[j] = y[idx[j]], idx as utils/sampling.py permuted_indices.
+// Does not advance step_dev; enqueue increment_i32 after it.
+void sample_gather(at::Tensor x, c10::optional<at::Tensor> y, at::Tensor xb,
+                   c10::optional<at::Tensor> yb, int64_t seed, at::Tensor step_dev,
+                   c10::optional<at::Tensor> idx_out) {
+  TORCH_CHECK(x.is_cuda() && x.is_contiguous() && x.dim() == 2, "x must be a contiguous GPU [n, F]");
+  TORCH_CHECK(x.scalar_type() == at::kBFloat16 || x.scalar_type() == at::kFloat,
+              "x must be bf16 or fp32");
+  const int64_t n = x.size(0), F = x.size(1), k = xb.size(0);
+  TORCH_CHECK(n >= 1 && n < (1LL << 31), "sample_gather needs 1 <= n < 2^31");
+  TORCH_CHECK(F >= 1 && F < (1 << 24), "sample_gather needs 1 <= F < 2^24");
+  check_gpu_contig(xb, x.scalar_type(), "xb");
+  TORCH_CHECK(xb.dim() == 2 && xb.size(1) == F && xb.device() == x.device(), "xb must be [k, F]");
+  TORCH_CHECK(k <= n, "sample_gather: batch ", k, " exceeds the ", n, " rows");
+  TORCH_CHECK(y.has_value() == yb.has_value(), "y and yb go together");
+  const void* yp = nullptr;
+  void* ybp = nullptr;
+  int64_t L = 0;
+  int y_es = 0;
+  if (y.has_value()) {
+    TORCH_CHECK(y->is_cuda() && y->is_contiguous() && y->dim() == 2 && y->size(0) == n &&
+                    y->device() == x.device(),
+                "y must be a contiguous GPU [n, L]");
+    TORCH_CHECK(y->scalar_type() == at::kFloat || y->scalar_type() == at::kLong,
+                "y must be fp32 or int64");
+    L = y->size(1);
+    TORCH_CHECK(L >= 1 && L < (1 << 24), "sample_gather needs 1 <= L < 2^24");
+    check_gpu_contig(*yb, y->scalar_type(), "yb");
+    TORCH_CHECK(yb->dim() == 2 && yb->size(0) == k && yb->size(1) == L &&
+                    yb->device() == x.device(),
+                "yb must be [k, L]");
+    yp = y->data_ptr();
+    ybp = yb->data_ptr();
+    y_es = (int)y->element_size();
+  }
+  check_gpu_contig(step_dev, at::kInt, "step_dev");
+  TORCH_CHECK(step_dev.numel() == 1 && step_dev.device() == x.device(), "step_dev is one int32");
+  int* ip = nullptr;
+  if (idx_out.has_value()) {
+    check_gpu_contig(*idx_out, at::kInt, "idx_out");
+    TORCH_CHECK(idx_out->numel() == k && idx_out->device() == x.device(), "idx_out must be [k]");
+    ip = idx_out->data_ptr<int>();
+  }
+  CHECK_HIP(launch_sample_gather(x.data_ptr(), (int)x.element_size(), yp, y_es, xb.data_ptr(), ybp,
+                                 ip, step_dev.data_ptr<int>(), (uint32_t)(seed & 0xFFFFFFFFLL), n,
+                                 (int)k, (int)F, (int)L, head_num_cus(), cur_stream()));
 }
 
 at::Tensor linear_head_bwd(at::Tensor dz_out, at::Tensor w, at::Tensor y_in, at::Tensor dw,
@@ -997,6 +1048,10 @@ at::Tensor bn_bwd_dx_nhwc(at::Tensor dy, c10::optional<at::Tensor> yrelu, at::Te
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("fused_adam", &fused_adam, "fused Adam on a flat bucket");
   m.def("increment_i32", &increment_i32, "device step counter += 1 (graph-capturable)");
+  m.def("sample_gather", &sample_gather,
+        "draw minibatch *step_dev under seed and gather its rows (graph-capturable)",
+        py::arg("x"), py::arg("y"), py::arg("xb"), py::arg("yb"), py::arg("seed"),
+        py::arg("step_dev"), py::arg("idx_out") = py::none());
   m.def("fused_sgd", &fused_sgd, "fused SGD on a flat bucket");
   m.def("relu_bwd", &relu_bwd, "dz = dy * (y>0)");
   m.def("bias_grad", &bias_grad, "column-sum of dz");

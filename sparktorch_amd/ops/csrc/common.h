@@ -43,6 +43,19 @@ __host__ __device__ __forceinline__ int64_t ceil_div_i64(int64_t a, int64_t b) {
   return (a + b - 1) / b;
 }
 
+// Counter-based hash (murmur3 finalizer over a * golden + seed): dropout masks
+// (conv.hip) and minibatch selection (sample_gather.hip; the same rule in
+// Python is sparktorch_amd/utils/sampling.py).
+__host__ __device__ __forceinline__ uint32_t hash_u32(uint32_t a, uint32_t seed) {
+  uint32_t h = a * 0x9E3779B9u + seed;
+  h ^= h >> 16;
+  h *= 0x85EBCA6Bu;
+  h ^= h >> 13;
+  h *= 0xC2B2AE35u;
+  h ^= h >> 16;
+  return h;
+}
+
 #define HIP_CHECK_LAUNCH()                                         \
   do {                                                             \
     hipError_t err_ = hipGetLastError();                           \

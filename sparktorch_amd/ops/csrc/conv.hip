@@ -170,15 +170,7 @@ extern "C" hipError_t launch_maxpool_bwd(const bf16raw* dy, const uint8_t* arg, 
 // same seed: zero mask-memory traffic.
 // ---------------------------------------------------------------------------
 
-__device__ __forceinline__ uint32_t hash_u32(uint32_t a, uint32_t seed) {
-  uint32_t h = a * 0x9E3779B9u + seed;
-  h ^= h >> 16;
-  h *= 0x85EBCA6Bu;
-  h ^= h >> 13;
-  h *= 0xC2B2AE35u;
-  h ^= h >> 16;
-  return h;
-}
+// hash_u32: common.h
 
 // unit id: element-wise (units_div=1), NCHW channel-wise (units_div=HW:
 // unit = idx/HW = b*C+c), or NHWC channel-wise (units_div=HWC, cmod=C:

@@ -26,6 +26,7 @@ import torch
 from sparktorch_amd.parallel.sync import compute_loss
 from sparktorch_amd.parallel.wire import decode_state_dict, encode_tensors
 from sparktorch_amd.utils.data import handle_features, handle_features_device
+from sparktorch_amd.utils.sampling import DeviceMinibatchSampler
 from sparktorch_amd.utils.trace import StepMetrics, trace_range
 from sparktorch_amd.utils.serialize import load_torch_model
 
@@ -123,6 +124,13 @@ def handle_model(
         side_stream = torch.cuda.Stream()  # hipMemcpyAsync H2D off the compute stream
 
     n = x_train.shape[0]
+    # GPU worker: minibatches drawn and gathered on the device, no host RNG
+    # or index upload per iteration (the model stays on its eager path)
+    sampler = None
+    if device.startswith("cuda") and 0 < mini_batch < n:
+        sampler = DeviceMinibatchSampler(
+            x_train, y_train if feats.y_train is not None else None, mini_batch
+        )
     metrics = StepMetrics()
     for i in range(iters):
         metrics.start()
@@ -140,7 +148,9 @@ def handle_model(
             torch.cuda.current_stream().wait_stream(side_stream)
         model.load_state_dict(sd)
 
-        if 0 < mini_batch < n:
+        if sampler is not None:
+            xb, yb = sampler.next()
+        elif 0 < mini_batch < n:
             idx = torch.from_numpy(np.random.choice(n, mini_batch, replace=False))
             xb, yb = x_train[idx], y_train[idx]
         else:

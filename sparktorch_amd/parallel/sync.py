@@ -41,6 +41,7 @@ from sparktorch_amd.parallel.rendezvous import (
 )
 from sparktorch_amd.utils.data import handle_features, handle_features_device
 from sparktorch_amd.utils.early_stopper import EarlyStopping
+from sparktorch_amd.utils.sampling import DeviceMinibatchSampler
 from sparktorch_amd.utils.trace import StepMetrics, trace_range
 from sparktorch_amd.utils.serialize import (
     load_base_torch,
@@ -123,6 +124,7 @@ class SyncTrainer:
 
         self._graph = None
         self._graph_inputs = None
+        self._sampled_graph = None  # (sampler, graph, static loss)
         self.compile_mode = compile_mode
         if compile_mode and compile_mode not in ("hipgraph",):
             # Correct implementation of the reference's broken torch.compile
@@ -236,6 +238,86 @@ class SyncTrainer:
         return float(static_loss)
 
     # ------------------------------------------------------------------
+    def _step_body(self, x: torch.Tensor, y: torch.Tensor, grad_scale: float) -> torch.Tensor:
+        self.buckets.zero_grad()
+        loss = self._forward_backward(x, y)
+        if self.optimizer is not None:
+            self.buckets.finalize(average=False)  # scale fused into the update
+            self.optimizer.step(grad_scale=grad_scale)
+        else:
+            self.buckets.finalize(average=True)
+            self._torch_opt.step()
+        return loss
+
+    def train_step_sampled(self, sampler) -> float:
+        """One step on the next minibatch of a
+        :class:`~sparktorch_amd.utils.sampling.DeviceMinibatchSampler`.
+
+        Eager: draw + gather, then the body of :meth:`train_step`.  With
+        ``compile_mode='hipgraph'`` on a GPU the draw, the gather and the
+        sampler's counter increment are captured together with zero + fwd +
+        bwd + fused step, so an iteration is one graph replay plus the loss
+        read and the host chooses nothing."""
+        if self.compile_mode == "hipgraph" and sampler.native:
+            return self._train_step_sampled_graphed(sampler)
+        xb, yb = sampler.next()
+        return float(self._step_body(xb, yb, 1.0 / self.world_size).detach())
+
+    def _train_step_sampled_graphed(self, sampler) -> float:
+        if self._sampled_graph is None or self._sampled_graph[0] is not sampler:
+            if self.world_size > 1:
+                raise RuntimeError(
+                    "compileMode='hipgraph' currently supports world_size==1 "
+                    "(collectives are not graph-captured)"
+                )
+            # As in _train_step_graphed: the two warmup steps really execute,
+            # so everything they mutate is put back before the first replay —
+            # here also the sampler's counter, or they would consume draws.
+            snap = [(t, t.clone()) for t in self._mutable_state()]
+            snap.append((sampler.step_dev, sampler.step_dev.clone()))
+            step_count = self.optimizer.step_count if self.optimizer is not None else None
+
+            def whole_step():
+                xb, yb = sampler.next()
+                return self._step_body(xb, yb, 1.0)
+
+            s = torch.cuda.Stream()
+            s.wait_stream(torch.cuda.current_stream())
+            with torch.cuda.stream(s):
+                for _ in range(2):
+                    whole_step()
+            torch.cuda.current_stream().wait_stream(s)
+            g = torch.cuda.CUDAGraph()
+            static_loss = torch.zeros((), device=sampler.step_dev.device)
+            with torch.cuda.graph(g):
+                static_loss.copy_(whole_step().detach())
+            for t, t0 in snap:
+                t.copy_(t0)
+            if step_count is not None:
+                self.optimizer.step_count = step_count
+            self._sampled_graph = (sampler, g, static_loss)
+        _, g, static_loss = self._sampled_graph
+        g.replay()
+        if self.optimizer is not None:
+            self.optimizer.step_count += 1  # host mirror of the device counter
+        return float(static_loss)
+
+    def _mutable_state(self) -> List[torch.Tensor]:
+        """Every tensor a train step writes and the next one reads."""
+        state = [b.flat_param for b in self.buckets.buckets]
+        state += [v for _, v in self.model.named_buffers()]
+        if self.optimizer is not None:
+            for name in ("exp_avg", "exp_avg_sq", "momentum_buf"):
+                state += [t for t in getattr(self.optimizer, name, []) if t is not None]
+            sd = getattr(self.optimizer, "step_dev", None)
+            if sd is not None:
+                state.append(sd)
+        else:
+            for st in self._torch_opt.state.values():
+                state += [t for t in st.values() if torch.is_tensor(t)]
+        return state
+
+    # ------------------------------------------------------------------
     @torch.no_grad()
     def validation_loss(self, x_val: torch.Tensor, y_val: torch.Tensor) -> float:
         self.model.eval()
@@ -319,18 +401,33 @@ def handle_model(
         comm_dev = dev if dev.startswith("cuda") else "cpu"
         metrics = StepMetrics()
 
-        for i in range(iters):
-            if 0 < mini_batch < n:
-                idx = torch.from_numpy(np.random.choice(n, mini_batch, replace=False))
-                xb = x_train[idx]
-                yb = y_train[idx]
-            else:
-                xb, yb = x_train, y_train
+        # GPU minibatches are drawn and gathered on the device (one seed from
+        # np.random here, nothing per iteration); the CPU path keeps the
+        # reference's per-iteration np.random.choice
+        sampler = None
+        if dev.startswith("cuda") and 0 < mini_batch < n:
+            sampler = DeviceMinibatchSampler(
+                x_train, y_train if data.y_train is not None else None, mini_batch
+            )
 
-            metrics.start()
-            with trace_range("train_step"):
-                loss = trainer.train_step(xb, yb)
-            metrics.stop(loss)
+        for i in range(iters):
+            if sampler is not None:
+                metrics.start()
+                with trace_range("train_step"):
+                    loss = trainer.train_step_sampled(sampler)
+                metrics.stop(loss)
+            else:
+                if 0 < mini_batch < n:
+                    idx = torch.from_numpy(np.random.choice(n, mini_batch, replace=False))
+                    xb = x_train[idx]
+                    yb = y_train[idx]
+                else:
+                    xb, yb = x_train, y_train
+
+                metrics.start()
+                with trace_range("train_step"):
+                    loss = trainer.train_step(xb, yb)
+                metrics.stop(loss)
 
             if es is not None:
                 loss_for_es = (
