@@ -50,6 +50,10 @@ int linear_wgrad_stream_supported(int, int, int64_t);
 int linear_wgrad_stream_can_run(int, int, int64_t);
 hipError_t launch_linear_wgrad_stream(const bf16raw*, const bf16raw*, float*, float*, int64_t, int,
                                       int, int, int, hipStream_t);
+int linear_fwd_stream_supported(int, int, int64_t);
+int64_t linear_fwd_stream_min_rows();
+hipError_t launch_linear_stream(const bf16raw*, const bf16raw*, bf16raw*, const float*,
+                                const bf16raw*, int64_t, int, int, int, int, int, hipStream_t);
 hipError_t launch_sample_gather(const void*, int, const void*, int, void*, void*, int*, const int*,
                                 uint32_t, int64_t, int, int, int, int, hipStream_t);
 hipError_t launch_head_bwd(const bf16raw*, const bf16raw*, const bf16raw*, bf16raw*, float*,
@@ -318,7 +322,52 @@ std::tuple<at::Tensor, at::Tensor> mse_fused(at::Tensor pred, at::Tensor target)
 // Linear family (see gemm.hip header comment for the stride mappings)
 // ---------------------------------------------------------------------------
 
-at::Tensor linear_fwd(at::Tensor x, at::Tensor w, c10::optional<at::Tensor> bias, bool relu) {
+// Full-N streaming route (linear_stream.hip) for C[M, n_out] = A[M, k_red] B
+// with a bf16 weight.  linear_fwd_stream_ok is the shape rule alone;
+// stream_route adds what the public bindings ask before they take it: a big
+// enough M and 16-byte aligned operands.  Forward and both dgrads share it,
+// so one shape always takes one route.
+bool linear_fwd_stream_ok(int64_t n_out, int64_t k_red, int64_t M) {
+  return n_out <= 256 && k_red < (1 << 24) &&
+         linear_fwd_stream_supported((int)n_out, (int)k_red, M) != 0;
+}
+
+static bool aligned16(const at::Tensor& t) { return (((uintptr_t)t.data_ptr()) & 15) == 0; }
+
+// Routing threshold: the measured one of linear_stream.hip unless a test has
+// set another (set_linear_stream_min_rows; negative = back to the measured).
+static int64_t g_stream_min_rows = -1;
+
+int64_t linear_stream_min_rows() {
+  return g_stream_min_rows >= 0 ? g_stream_min_rows : linear_fwd_stream_min_rows();
+}
+
+int64_t set_linear_stream_min_rows(int64_t rows) {
+  const int64_t old = g_stream_min_rows;
+  g_stream_min_rows = rows;
+  return old;
+}
+
+static bool stream_route(const at::Tensor& a, const at::Tensor& w, int64_t n_out, int64_t k_red,
+                         int64_t M) {
+  return w.scalar_type() == at::kBFloat16 && M >= linear_stream_min_rows() &&
+         linear_fwd_stream_ok(n_out, k_red, M) && aligned16(a) && aligned16(w);
+}
+
+static int fwd_epi(const c10::optional<at::Tensor>& bias, bool relu, const float** bptr) {
+  *bptr = nullptr;
+  if (bias.has_value()) {
+    check_gpu_contig(*bias, at::kFloat, "bias");
+    *bptr = bias->data_ptr<float>();
+    return relu ? 3 : 2;  // EPI_BIAS_RELU : EPI_BIAS
+  }
+  return relu ? 4 : 1;  // EPI_RELU : EPI_BF16
+}
+
+// allow_stream = false pins the call to gemm.hip's tiles (the conv col
+// matrices: their shapes were tuned on those tiles).
+at::Tensor linear_fwd(at::Tensor x, at::Tensor w, c10::optional<at::Tensor> bias, bool relu,
+                      bool allow_stream) {
   check_gpu_contig(x, at::kBFloat16, "x");
   TORCH_CHECK(w.is_cuda() && w.is_contiguous(), "w must be contiguous GPU");
   TORCH_CHECK(w.scalar_type() == at::kFloat || w.scalar_type() == at::kBFloat16);
@@ -326,13 +375,12 @@ at::Tensor linear_fwd(at::Tensor x, at::Tensor w, c10::optional<at::Tensor> bias
   TORCH_CHECK(w.size(1) == K, "shape mismatch");
   auto y = at::empty({M, N}, x.options());
   const float* bptr = nullptr;
-  int epi = 1;  // EPI_BF16
-  if (bias.has_value()) {
-    check_gpu_contig(*bias, at::kFloat, "bias");
-    bptr = bias->data_ptr<float>();
-    epi = relu ? 3 : 2;
-  } else if (relu) {
-    epi = 4;  // EPI_RELU
+  const int epi = fwd_epi(bias, relu, &bptr);
+  if (allow_stream && stream_route(x, w, N, K, M)) {
+    CHECK_HIP(launch_linear_stream((const bf16raw*)x.data_ptr(), (const bf16raw*)w.data_ptr(),
+                                   (bf16raw*)y.data_ptr(), bptr, nullptr, M, (int)N, (int)K, epi,
+                                   /*b_kn*/ 0, 0, cur_stream()));
+    return y;
   }
   CHECK_HIP(launch_gemm_bf16(x.data_ptr(), w.data_ptr(), w.scalar_type() == at::kFloat ? 1 : 0,
                              nullptr, (bf16raw*)y.data_ptr(), bptr, (int)M, (int)N, (int)K,
@@ -340,12 +388,36 @@ at::Tensor linear_fwd(at::Tensor x, at::Tensor w, c10::optional<at::Tensor> bias
   return y;
 }
 
-at::Tensor linear_dgrad(at::Tensor dz, at::Tensor w) {
+// The streaming kernel at any M (tests, microbenchmarks); bf16 w only.
+at::Tensor linear_fwd_stream(at::Tensor x, at::Tensor w, c10::optional<at::Tensor> bias,
+                             bool relu) {
+  check_gpu_contig(x, at::kBFloat16, "x");
+  check_gpu_contig(w, at::kBFloat16, "w");
+  TORCH_CHECK(x.dim() == 2 && w.dim() == 2 && w.size(1) == x.size(1), "shape mismatch");
+  int64_t M = x.size(0), K = x.size(1), N = w.size(0);
+  TORCH_CHECK(linear_fwd_stream_ok(N, K, M), "linear_fwd_stream: unsupported (N, K, M)");
+  TORCH_CHECK(aligned16(x) && aligned16(w), "linear_fwd_stream wants 16-byte aligned x and w");
+  auto y = at::empty({M, N}, x.options());
+  const float* bptr = nullptr;
+  const int epi = fwd_epi(bias, relu, &bptr);
+  CHECK_HIP(launch_linear_stream((const bf16raw*)x.data_ptr(), (const bf16raw*)w.data_ptr(),
+                                 (bf16raw*)y.data_ptr(), bptr, nullptr, M, (int)N, (int)K, epi, 0,
+                                 0, cur_stream()));
+  return y;
+}
+
+at::Tensor linear_dgrad(at::Tensor dz, at::Tensor w, bool allow_stream) {
   check_gpu_contig(dz, at::kBFloat16, "dz");
   TORCH_CHECK(w.is_cuda() && w.is_contiguous());
   int64_t M = dz.size(0), N = dz.size(1), K = w.size(1);
   TORCH_CHECK(w.size(0) == N, "shape mismatch");
   auto dx = at::empty({M, K}, dz.options());
+  if (allow_stream && stream_route(dz, w, K, N, M)) {
+    CHECK_HIP(launch_linear_stream((const bf16raw*)dz.data_ptr(), (const bf16raw*)w.data_ptr(),
+                                   (bf16raw*)dx.data_ptr(), nullptr, nullptr, M, (int)K, (int)N,
+                                   /*EPI_BF16*/ 1, /*b_kn*/ 1, 0, cur_stream()));
+    return dx;
+  }
   CHECK_HIP(launch_gemm_bf16(dz.data_ptr(), w.data_ptr(), w.scalar_type() == at::kFloat ? 1 : 0,
                              nullptr, (bf16raw*)dx.data_ptr(), nullptr, (int)M, (int)K, (int)N,
                              /*sam*/ N, /*sak*/ 1, /*sbk*/ K, /*sbn*/ 1, 1, 1, nullptr, -1, cur_stream()));
@@ -353,9 +425,9 @@ at::Tensor linear_dgrad(at::Tensor dz, at::Tensor w) {
 }
 
 // dX = (dZ W) * (y_prev > 0): linear_dgrad with the producer layer's ReLU
-// backward folded into the C-write (gemm.hip EPI_BF16_MASK); bit-identical
-// to relu_bwd(linear_dgrad(dz, w), y_prev).
-at::Tensor linear_dgrad_relu(at::Tensor dz, at::Tensor w, at::Tensor y_prev) {
+// backward folded into the C-write (EPI_BF16_MASK in gemm.hip and
+// linear_stream.hip); bit-identical to relu_bwd(linear_dgrad(dz, w), y_prev).
+at::Tensor linear_dgrad_relu(at::Tensor dz, at::Tensor w, at::Tensor y_prev, bool allow_stream) {
   check_gpu_contig(dz, at::kBFloat16, "dz");
   check_gpu_contig(y_prev, at::kBFloat16, "y_prev");
   TORCH_CHECK(w.is_cuda() && w.is_contiguous());
@@ -364,11 +436,41 @@ at::Tensor linear_dgrad_relu(at::Tensor dz, at::Tensor w, at::Tensor y_prev) {
   TORCH_CHECK(y_prev.dim() == 2 && y_prev.size(0) == M && y_prev.size(1) == K,
               "y_prev must be [M, K_in]");
   auto dx = at::empty({M, K}, dz.options());
+  if (allow_stream && stream_route(dz, w, K, N, M) && aligned16(y_prev)) {
+    CHECK_HIP(launch_linear_stream((const bf16raw*)dz.data_ptr(), (const bf16raw*)w.data_ptr(),
+                                   (bf16raw*)dx.data_ptr(), nullptr,
+                                   (const bf16raw*)y_prev.data_ptr(), M, (int)K, (int)N,
+                                   /*EPI_BF16_MASK*/ 6, /*b_kn*/ 1, 0, cur_stream()));
+    return dx;
+  }
   CHECK_HIP(launch_gemm_bf16_mask(dz.data_ptr(), w.data_ptr(),
                                   w.scalar_type() == at::kFloat ? 1 : 0, nullptr,
                                   (bf16raw*)dx.data_ptr(), nullptr, (int)M, (int)K, (int)N,
                                   /*sam*/ N, /*sak*/ 1, /*sbk*/ K, /*sbn*/ 1, 6, 1, nullptr, -1,
                                   (const bf16raw*)y_prev.data_ptr(), cur_stream()));
+  return dx;
+}
+
+// The streaming dgrad at any M; y_prev present = the masked form.
+at::Tensor linear_dgrad_stream(at::Tensor dz, at::Tensor w, c10::optional<at::Tensor> y_prev) {
+  check_gpu_contig(dz, at::kBFloat16, "dz");
+  check_gpu_contig(w, at::kBFloat16, "w");
+  TORCH_CHECK(dz.dim() == 2 && w.dim() == 2 && w.size(0) == dz.size(1), "shape mismatch");
+  int64_t M = dz.size(0), N = dz.size(1), K = w.size(1);
+  TORCH_CHECK(linear_fwd_stream_ok(K, N, M), "linear_dgrad_stream: unsupported (K_in, N_out, M)");
+  TORCH_CHECK(aligned16(dz) && aligned16(w), "linear_dgrad_stream wants 16-byte aligned dz and w");
+  const bf16raw* mptr = nullptr;
+  if (y_prev.has_value()) {
+    check_gpu_contig(*y_prev, at::kBFloat16, "y_prev");
+    TORCH_CHECK(y_prev->dim() == 2 && y_prev->size(0) == M && y_prev->size(1) == K,
+                "y_prev must be [M, K_in]");
+    TORCH_CHECK(aligned16(*y_prev), "linear_dgrad_stream wants a 16-byte aligned y_prev");
+    mptr = (const bf16raw*)y_prev->data_ptr();
+  }
+  auto dx = at::empty({M, K}, dz.options());
+  CHECK_HIP(launch_linear_stream((const bf16raw*)dz.data_ptr(), (const bf16raw*)w.data_ptr(),
+                                 (bf16raw*)dx.data_ptr(), nullptr, mptr, M, (int)K, (int)N,
+                                 mptr ? 6 : 1, /*b_kn*/ 1, 0, cur_stream()));
   return dx;
 }
 
@@ -1071,9 +1173,26 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("cast_f32_bf16", &cast_f32_bf16);
   m.def("ce_fused", &ce_fused, "cross-entropy fwd+bwd fused");
   m.def("mse_fused", &mse_fused, "mse fwd+bwd fused");
-  m.def("linear_fwd", &linear_fwd, "Y = X W^T (+bias)(+relu), MFMA");
-  m.def("linear_dgrad", &linear_dgrad, "dX = dZ W, MFMA");
-  m.def("linear_dgrad_relu", &linear_dgrad_relu, "dX = (dZ W) * (y_prev > 0), MFMA");
+  m.def("linear_fwd", &linear_fwd, "Y = X W^T (+bias)(+relu), MFMA", py::arg("x"), py::arg("w"),
+        py::arg("bias"), py::arg("relu"), py::arg("allow_stream") = true);
+  m.def("linear_dgrad", &linear_dgrad, "dX = dZ W, MFMA", py::arg("dz"), py::arg("w"),
+        py::arg("allow_stream") = true);
+  m.def("linear_fwd_stream_supported", &linear_fwd_stream_ok,
+        "can the full-N streaming Linear kernel compute C[M, N] from a K-deep reduction",
+        py::arg("N"), py::arg("K"), py::arg("M"));
+  m.def("linear_fwd_stream_min_rows", &linear_stream_min_rows,
+        "M from which linear_fwd / linear_dgrad(_relu) route supported shapes to it");
+  m.def("set_linear_stream_min_rows", &set_linear_stream_min_rows,
+        "override that M (tests); negative restores the measured one; returns the old setting",
+        py::arg("rows"));
+  m.def("linear_fwd_stream", &linear_fwd_stream,
+        "Y = X W^T (+bias)(+relu) through the full-N streaming kernel, any M", py::arg("x"),
+        py::arg("w"), py::arg("bias"), py::arg("relu"));
+  m.def("linear_dgrad_stream", &linear_dgrad_stream,
+        "dX = dZ W (* (y_prev > 0)) through the full-N streaming kernel, any M", py::arg("dz"),
+        py::arg("w"), py::arg("y_prev") = py::none());
+  m.def("linear_dgrad_relu", &linear_dgrad_relu, "dX = (dZ W) * (y_prev > 0), MFMA",
+        py::arg("dz"), py::arg("w"), py::arg("y_prev"), py::arg("allow_stream") = true);
   m.def("head_bwd_supported", &head_bwd_ok, "does the one-pass head backward serve (C, H)");
   m.def("linear_head_bwd", &linear_head_bwd, "one-pass dz_in/dW/db of a small head on a ReLU layer",
         py::arg("dz_out"), py::arg("w"), py::arg("y_in"), py::arg("dw"), py::arg("db"),

@@ -28,8 +28,10 @@
 //
 // One kernel serves the forward and both gradients of Linear/conv via strides
 // (big-batch Linear dW+db with 64/128/256 outputs streams through
-// linear_wgrad.hip instead; conv col-matrix, small-batch and odd-shape wgrads
-// stay here):
+// linear_wgrad.hip instead, and big-batch Linear fwd / dX with 128 < N <= 256
+// output columns and a bf16 weight through linear_stream.hip, where one block
+// owns all N columns of its rows; conv col-matrix, small-batch and odd-shape
+// GEMMs stay here):
 //   fwd   Y = X  W^T : A=X(row),   B=W^T (sbk=1,   sbn=K)    [A glds, B glds if bf16]
 //   dX    = dZ W     : A=dZ(row),  B=W   (sbk=Kin, sbn=1)    [A glds]
 //   dW    = dZ^T X   : A=dZ^T (sam=1, sak=N), B=X (sbk=Kin, sbn=1), split-K

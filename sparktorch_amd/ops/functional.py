@@ -109,6 +109,11 @@ def _linear_param_grads(ext, dz, x, w, b, need_w: bool, need_b: bool):
     return dw, db
 
 
+# Tests flip this to pin Linear forward / dgrad to gemm.hip's tiles; on, the
+# bindings route big-batch N in (128, 256] shapes to linear_stream.hip.
+_LINEAR_STREAM = True
+
+
 class _LinearFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x: torch.Tensor, w: torch.Tensor, b: Optional[torch.Tensor], relu: bool):
@@ -116,7 +121,7 @@ class _LinearFn(torch.autograd.Function):
         # of re-reading + converting the fp32 master per M-tile (the cast
         # point is where the stage converted anyway — numerics unchanged)
         wb = ops.ext().cast_f32_bf16(w) if w.dtype == torch.float32 else w
-        y = ops.ext().linear_fwd(x, wb, b, relu)
+        y = ops.ext().linear_fwd(x, wb, b, relu, _LINEAR_STREAM)
         # wb rides save_for_backward so autograd's saved-tensor versioning
         # covers it (in-place mutation of w between fwd and bwd is detected);
         # only the Parameter reference for _bucket_notify stays an attribute.
@@ -134,7 +139,7 @@ class _LinearFn(torch.autograd.Function):
         if dy.dtype != torch.bfloat16:
             dy = dy.to(torch.bfloat16)
         dz = ext.relu_bwd(dy, y) if ctx.relu else dy
-        dx = ext.linear_dgrad(dz, wb) if ctx.needs_input_grad[0] else None
+        dx = ext.linear_dgrad(dz, wb, _LINEAR_STREAM) if ctx.needs_input_grad[0] else None
 
         dw, db = _linear_param_grads(ext, dz, x, w, ctx.bias_ref, ctx.needs_input_grad[1],
                                      ctx.has_bias and ctx.needs_input_grad[2])
@@ -209,7 +214,7 @@ class _MLPChainFn(torch.autograd.Function):
         for i in range(n):
             w, b = params[2 * i], params[2 * i + 1]
             wb = ext.cast_f32_bf16(w) if w.dtype == torch.float32 else w
-            h = ext.linear_fwd(h, wb, b, relus[i])
+            h = ext.linear_fwd(h, wb, b, relus[i], _LINEAR_STREAM)
             saved += [w, wb, h]
             biases.append(b)
         ctx.save_for_backward(*saved)
@@ -244,9 +249,9 @@ class _MLPChainFn(torch.autograd.Function):
                 continue
             dz_prev = None
             if masked:
-                dz_prev = ext.linear_dgrad_relu(dz, wb, xin)
+                dz_prev = ext.linear_dgrad_relu(dz, wb, xin, _LINEAR_STREAM)
             elif i > 0 or ctx.needs_input_grad[0]:
-                dz_prev = ext.linear_dgrad(dz, wb)
+                dz_prev = ext.linear_dgrad(dz, wb, _LINEAR_STREAM)
             grads[2 * i], grads[2 * i + 1] = _linear_param_grads(ext, dz, xin, w, b, need_w,
                                                                  need_b)
             dz = dz_prev
@@ -312,7 +317,7 @@ class _Conv2dFn(torch.autograd.Function):
         WO = (W + 2 * pw - KW) // sw + 1
         col = ext.im2col(x, KH, KW, sh, sw, ph, pw)
         w2d = w.reshape(CO, CI * KH * KW).contiguous()
-        y2d = ext.linear_fwd(col, w2d, b, relu)  # [B*HO*WO, CO]
+        y2d = ext.linear_fwd(col, w2d, b, relu, allow_stream=False)  # [B*HO*WO, CO]
         ctx.save_for_backward(col, w2d, y2d)
         ctx.meta = (B, CI, H, W, CO, KH, KW, sh, sw, ph, pw, HO, WO, relu, b is not None)
         ctx.w_ref, ctx.b_ref = w, b
@@ -347,7 +352,7 @@ class _Conv2dFn(torch.autograd.Function):
 
         dx = None
         if ctx.needs_input_grad[0]:
-            dcol = ext.linear_dgrad(dz, w2d)
+            dcol = ext.linear_dgrad(dz, w2d, allow_stream=False)
             dx = ext.col2im(dcol, B, CI, H, W, KH, KW, sh, sw, ph, pw)
         return dx, dw, db, None, None, None
 
@@ -387,7 +392,7 @@ class _Conv2dNHWCFn(torch.autograd.Function):
         # DMA-staged; fp32->bf16 happened at the LDS stage before, so the
         # compute numerics are unchanged
         w2d = w2d.to(torch.bfloat16).contiguous()
-        y2d = ext.linear_fwd(col, w2d, b, relu)  # [B*HO*WO, CO] == NHWC
+        y2d = ext.linear_fwd(col, w2d, b, relu, allow_stream=False)  # [B*HO*WO, CO] == NHWC
         ctx.save_for_backward(col, w2d, y2d)
         ctx.meta = (B, CI, H, W, CO, KH, KW, sh, sw, ph, pw, HO, WO, relu, b is not None)
         ctx.b_ref = b
@@ -419,7 +424,7 @@ class _Conv2dNHWCFn(torch.autograd.Function):
 
         dx = None
         if ctx.needs_input_grad[0]:
-            dcol = ext.linear_dgrad(dz, w2d)
+            dcol = ext.linear_dgrad(dz, w2d, allow_stream=False)
             dx = ext.col2im_nhwc(dcol, B, CI, H, W, KH, KW, sh, sw, ph, pw)
         return dx, dw, db, None, None, None
 
@@ -497,7 +502,7 @@ class _ConvImplicitNHWCFn(torch.autograd.Function):
             else:
                 # strided dgrad is a transposed conv — scatter dcol back
                 # (col2im only; no im2col anywhere on this path)
-                dcol = ext.linear_dgrad(dz, _pad64(w2d).contiguous())
+                dcol = ext.linear_dgrad(dz, _pad64(w2d).contiguous(), allow_stream=False)
                 dx = ext.col2im_nhwc(dcol, B, CI, H, W, KH, KW, s, s, p, p)
         return dx, dw, db, None, None, None
 
