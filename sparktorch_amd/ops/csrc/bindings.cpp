@@ -58,6 +58,8 @@ hipError_t launch_sample_gather(const void*, int, const void*, int, void*, void*
                                 uint32_t, int64_t, int, int, int, int, hipStream_t);
 hipError_t launch_head_bwd(const bf16raw*, const bf16raw*, const bf16raw*, bf16raw*, float*,
                            float*, int, int, int, int, int, hipStream_t);
+hipError_t launch_head_ce(const bf16raw*, const float*, const bf16raw*, const int64_t*, bf16raw*,
+                          float*, float*, float*, bf16raw*, int, int, int, int, int, hipStream_t);
 hipError_t launch_bn_stats(const bf16raw*, float*, float*, float*, float*, float*, float*, int,
                            int, int64_t, float, float, int, hipStream_t);
 hipError_t launch_bn_apply(const bf16raw*, const bf16raw*, bf16raw*, const float*, const float*,
@@ -568,6 +570,48 @@ at::Tensor linear_head_bwd(at::Tensor dz_out, at::Tensor w, at::Tensor y_in, at:
                             dw.data_ptr<float>(), dbp, (int)B, (int)C, (int)H, (int)max_blocks,
                             head_num_cus(), cur_stream()));
   return dz_in;
+}
+
+// Head forward + mean cross-entropy + head backward in one pass over y_in
+// (head_bwd.hip, head_ce_kernel): returns (loss, dz_in, logits or an empty
+// tensor); dw / db are accumulated into, the loss is defined by the call.
+std::tuple<at::Tensor, at::Tensor, at::Tensor> linear_head_ce(
+    at::Tensor y_in, at::Tensor w, c10::optional<at::Tensor> bias, at::Tensor target,
+    at::Tensor dw, c10::optional<at::Tensor> db, bool want_logits, int64_t max_blocks) {
+  check_gpu_contig(y_in, at::kBFloat16, "y_in");
+  check_gpu_contig(w, at::kBFloat16, "w");
+  check_gpu_contig(target, at::kLong, "target");
+  check_gpu_contig(dw, at::kFloat, "dw");
+  TORCH_CHECK(y_in.dim() == 2 && w.dim() == 2 && target.dim() == 1);
+  int64_t B = y_in.size(0), H = y_in.size(1), C = w.size(0);
+  TORCH_CHECK(B >= 1 && B < (1LL << 31) && w.size(1) == H && target.size(0) == B &&
+                  dw.dim() == 2 && dw.size(0) == C && dw.size(1) == H,
+              "shape mismatch");
+  TORCH_CHECK(head_bwd_ok(C, H), "linear_head_ce: unsupported (C, H); use the three-step route");
+  const float* bp = nullptr;
+  if (bias.has_value()) {
+    check_gpu_contig(*bias, at::kFloat, "bias");
+    TORCH_CHECK(bias->numel() == C);
+    bp = bias->data_ptr<float>();
+  }
+  float* dbp = nullptr;
+  if (db.has_value()) {
+    check_gpu_contig(*db, at::kFloat, "db");
+    TORCH_CHECK(db->numel() == C);
+    dbp = db->data_ptr<float>();
+  }
+  auto loss = at::empty({}, y_in.options().dtype(at::kFloat));
+  auto dz_in = at::empty({B, H}, y_in.options());
+  auto logits = want_logits ? at::empty({B, C}, y_in.options()) : at::empty({0}, y_in.options());
+  TORCH_CHECK(((uintptr_t)y_in.data_ptr() & 15) == 0 && ((uintptr_t)dz_in.data_ptr() & 15) == 0 &&
+                  ((uintptr_t)w.data_ptr() & 15) == 0,
+              "linear_head_ce wants 16-byte aligned activations and weights");
+  CHECK_HIP(launch_head_ce((const bf16raw*)w.data_ptr(), bp, (const bf16raw*)y_in.data_ptr(),
+                           target.data_ptr<int64_t>(), (bf16raw*)dz_in.data_ptr(),
+                           dw.data_ptr<float>(), dbp, loss.data_ptr<float>(),
+                           want_logits ? (bf16raw*)logits.data_ptr() : nullptr, (int)B, (int)C,
+                           (int)H, (int)max_blocks, head_num_cus(), cur_stream()));
+  return {loss, dz_in, logits};
 }
 
 
@@ -1197,6 +1241,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("linear_head_bwd", &linear_head_bwd, "one-pass dz_in/dW/db of a small head on a ReLU layer",
         py::arg("dz_out"), py::arg("w"), py::arg("y_in"), py::arg("dw"), py::arg("db"),
         py::arg("max_blocks") = 0);
+  m.def("linear_head_ce", &linear_head_ce,
+        "head forward + cross-entropy + one-pass head backward: (loss, dz_in, logits)",
+        py::arg("y_in"), py::arg("w"), py::arg("bias"), py::arg("target"), py::arg("dw"),
+        py::arg("db"), py::arg("want_logits") = false, py::arg("max_blocks") = 0);
   m.def("linear_wgrad_stream_supported", &linear_wgrad_stream_ok,
         "is (No, Ki) at batch B routed to the batch-streaming wgrad");
   m.def("linear_wgrad_stream_can_run", &linear_wgrad_stream_runs,

@@ -56,7 +56,12 @@ __host__ __device__ __forceinline__ uint32_t hash_u32(uint32_t a, uint32_t seed)
   return h;
 }
 
-#define HIP_CHECK_LAUNCH()                                         \
+// Cross-entropy over C < 128 classes sums a row's exponentials by a lane
+// butterfly up to this batch (ce_fused_wave_kernel) and class-ascending above
+// it (ce_fused_kernel); head_bwd.hip's head_ce_kernel follows the same rule.
+#define CE_WAVE_MAX_B 2048
+
+#define HIP_CHECK_LAUNCH()                                        \
   do {                                                             \
     hipError_t err_ = hipGetLastError();                           \
     if (err_ != hipSuccess) return err_;                           \

@@ -29,6 +29,15 @@
 // wave owns 32-column groups of H for both products; w fragments and the
 // dW/db accumulators stay in registers across all of a block's tiles and
 // are flushed once with fp32 atomicAdd.
+//
+// head_ce_kernel runs the same tile loop for a train step under mean
+// cross-entropy: it needs no dz_out from memory.  Once a y_in tile is in LDS
+// it computes the tile's logits from that image (one wave per 16 rows, w as
+// a second set of register fragments), applies loss.hip's softmax / loss
+// arithmetic per row and writes the bf16 dlogits into the [rows][16] image
+// itself; an LDS-only barrier publishes the image and the two stages above
+// run unchanged.  The head's forward, the loss and the head's backward then
+// read y_in once and the logits never reach HBM (profiles/head_ce.md).
 
 #include "common.h"
 
@@ -67,11 +76,16 @@ __device__ __forceinline__ hfrag_t head_tr_frag(const bf16raw* __restrict__ img,
   return f;
 }
 
-template <int H, bool TR>
-__global__ __launch_bounds__(HEAD_THREADS, 2) void head_bwd_kernel(
+// Tile loop shared by head_bwd_kernel (CE = false: the dz_out image is staged
+// from global memory) and head_ce_kernel (CE = true: the image is computed
+// from the resident y_in tile; dz_out is unused).
+template <int H, bool TR, bool CE>
+__device__ __forceinline__ void head_tiles(
     const bf16raw* __restrict__ dz_out, const bf16raw* __restrict__ w,
     const bf16raw* __restrict__ y_in, bf16raw* __restrict__ dz_in, float* __restrict__ dw,
-    float* __restrict__ db, int B, int C) {
+    float* __restrict__ db, int B, int C, const float* __restrict__ bias,
+    const int64_t* __restrict__ tgt, float* __restrict__ loss, bf16raw* __restrict__ logits_out,
+    float inv_B) {
   constexpr int ROWS = head_rows(H);
   constexpr int SLOTS = H / 8;                     // 16 B slots per image row
   constexpr int XM = (SLOTS % 16 == 0) ? 15 : 7;   // slot ^= row & XM
@@ -82,7 +96,8 @@ __global__ __launch_bounds__(HEAD_THREADS, 2) void head_bwd_kernel(
   static_assert(H % 64 == 0 && H <= 512, "unsupported H");
 
   __shared__ __attribute__((aligned(16))) bf16raw ys[2][ROWS * H];
-  __shared__ __attribute__((aligned(16))) bf16raw dzs[2][ROWS * HEAD_CPAD];
+  // CE fills and consumes the dz image inside one tile step: one buffer
+  __shared__ __attribute__((aligned(16))) bf16raw dzs[CE ? 1 : 2][ROWS * HEAD_CPAD];
 
   const int t = threadIdx.x;
   const int wid = t >> 6, lane = t & 63;
@@ -111,6 +126,30 @@ __global__ __launch_bounds__(HEAD_THREADS, 2) void head_bwd_kernel(
 
   floatx4 accw[PW][2] = {};
   floatx4 accb = {0.f, 0.f, 0.f, 0.f};
+
+  // CE: w again as the forward's B operand (N = class, k ascending as in
+  // gemm_kernel: lane (class l15, q) holds k = ks*32 + q*8 .. +7), the
+  // lane's bias, next tile's targets and the block's loss
+  hfrag_t wk[CE ? H / 32 : 1];
+  float bias_c = 0.f, lsum = 0.f;
+  int tg[4] = {0, 0, 0, 0};
+  if (CE) {
+#pragma unroll
+    for (int ks = 0; ks < H / 32; ++ks) {
+      wk[ks] = hfrag_t{};
+      if (l15 < C) wk[ks] = *(const hfrag_t*)&w[l15 * H + ks * 32 + q * 8];
+    }
+    if (bias != nullptr && l15 < C) bias_c = bias[l15];
+  }
+  // targets of the rows whose logits this lane receives (wave wid owns tile
+  // rows wid*16 .. +15; accumulator element r <-> row wid*16 + q*4 + r)
+  auto load_tgt = [&](int tile) {
+    if (wid < ROWS / 16) {
+      const int64_t gr = (int64_t)tile * ROWS + wid * 16 + q * 4;
+#pragma unroll
+      for (int r = 0; r < 4; ++r) tg[r] = (gr + r < B) ? (int)tgt[gr + r] : 0;
+    }
+  };
 
   // dz_out tile -> registers (class dim zero-padded, rows past B zero)
   const int zrow = (t * EPT) / HEAD_CPAD, zc0 = (t * EPT) % HEAD_CPAD;
@@ -146,20 +185,113 @@ __global__ __launch_bounds__(HEAD_THREADS, 2) void head_bwd_kernel(
   int buf = 0;
   if (tile < ntiles) {
     dma_y(0, tile);
-    load_dz(tile);
-    write_dz(0);
+    if (CE) {
+      load_tgt(tile);
+    } else {
+      load_dz(tile);
+      write_dz(0);
+    }
   }
   for (; tile < ntiles; tile += gridDim.x) {
     // tile's images are complete and every wave is done with the other pair
-    __syncthreads();
+    // (CE says so itself: each wave's DMA of this tile has landed)
+    if (CE)
+      asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)\n\ts_barrier" ::: "memory");
+    else
+      __syncthreads();
     const int next = tile + gridDim.x;
-    if (next < ntiles) {
+    const bf16raw* yb = ys[buf];
+    bf16raw* zb = dzs[CE ? 0 : buf];
+    const int64_t row0 = (int64_t)tile * ROWS;
+    if (CE) {
+      int tc[4];
+#pragma unroll
+      for (int r = 0; r < 4; ++r) tc[r] = tg[r];
+      // The forward's y_in fragments are read before the next tile's DMA is
+      // issued (LDS reads after it wait for it to land), so the logits and
+      // the softmax run under the DMA.  H = 512 has no registers for that.
+      constexpr bool EARLY = H <= 256;
+      const bool fwd_wave = wid < ROWS / 16;  // one 16-row fragment per wave
+      const int arow = wid * 16 + l15;
+      hfrag_t ay[H / 32];
+      if (EARLY && fwd_wave) {
+#pragma unroll
+        for (int ks = 0; ks < H / 32; ++ks)
+          ay[ks] = *(const hfrag_t*)&yb[arow * H + (((ks * 4 + q) ^ (arow & XM)) << 3)];
+      }
+      if (next < ntiles) {
+        dma_y(buf ^ 1, next);
+        load_tgt(next);
+      }
+      // ---- logits, softmax, loss and the dz image of this tile ----
+      if (fwd_wave) {
+#pragma clang fp reassociate(off)  // the class sums keep loss.hip's order
+        floatx4 lg = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+        for (int ks = 0; ks < H / 32; ++ks) {
+          if (!EARLY)
+            ay[ks] = *(const hfrag_t*)&yb[arow * H + (((ks * 4 + q) ^ (arow & XM)) << 3)];
+          lg = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ay[ks], wk[ks], lg, 0, 0, 0);
+        }
+        // lane (class l15, q), element r <-> tile row wid*16 + q*4 + r.  The
+        // per-row arithmetic is loss.hip's; RG rows go side by side so their
+        // lane exchanges overlap (H = 512 has the registers for one).
+        constexpr int RG = H <= 256 ? 4 : 1;
+#pragma unroll
+        for (int r0 = 0; r0 < 4; r0 += RG) {
+          bf16raw xb[RG];
+          float x[RG], mx[RG], e[RG], se[RG];
+#pragma unroll
+          for (int j = 0; j < RG; ++j) {
+            xb[j] = f32_to_bf16(bias != nullptr ? lg[r0 + j] + bias_c : lg[r0 + j]);
+            x[j] = bf16_to_f32(xb[j]);
+            mx[j] = l15 < C ? fmaxf(-1e30f, x[j]) : -1e30f;
+          }
+#pragma unroll
+          for (int off = 8; off; off >>= 1)
+#pragma unroll
+            for (int j = 0; j < RG; ++j) mx[j] = fmaxf(mx[j], __shfl_xor(mx[j], off, 16));
+#pragma unroll
+          for (int j = 0; j < RG; ++j) e[j] = l15 < C ? __expf(x[j] - mx[j]) : 0.f;
+          if (B <= CE_WAVE_MAX_B) {  // ce_fused_wave_kernel's butterfly
+#pragma unroll
+            for (int j = 0; j < RG; ++j) se[j] = e[j];
+#pragma unroll
+            for (int off = 8; off; off >>= 1)
+#pragma unroll
+              for (int j = 0; j < RG; ++j) se[j] += __shfl_xor(se[j], off, 16);
+          } else {  // ce_fused_kernel's class-ascending sum
+#pragma unroll
+            for (int j = 0; j < RG; ++j) se[j] = 0.f;
+            for (int c = 0; c < C; ++c)
+#pragma unroll
+              for (int j = 0; j < RG; ++j) se[j] += __shfl(e[j], c, 16);
+          }
+#pragma unroll
+          for (int j = 0; j < RG; ++j) {
+            const int r = r0 + j;
+            const int lrow = wid * 16 + q * 4 + r;
+            const bool live = row0 + lrow < B;
+            const float xt = __shfl(x[j], tc[r] & 15, 16);
+            const float inv_se = 1.f / se[j];
+            // the target class in one fma: loss.hip's kernels compile to it
+            // under -ffast-math, and dz must keep their bits
+            const float p =
+                l15 == tc[r] ? __builtin_fmaf(e[j], inv_se, -1.f) : e[j] * inv_se;
+            zb[lrow * HEAD_CPAD + l15] =
+                (live && l15 < C) ? f32_to_bf16(p * inv_B) : (bf16raw)0;
+            if (live && l15 == 0) lsum += (__logf(se[j]) + mx[j] - xt) * inv_B;
+            if (logits_out != nullptr && live && l15 < C)
+              logits_out[(row0 + lrow) * C + l15] = xb[j];
+          }
+        }
+      }
+      // publish the dz image; the next tile's DMA stays in flight
+      asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
+    } else if (next < ntiles) {
       load_dz(next);
       dma_y(buf ^ 1, next);
     }
-    const bf16raw* yb = ys[buf];
-    const bf16raw* zb = dzs[buf];
-    const int64_t row0 = (int64_t)tile * ROWS;
 
     // ---- dgrad + mask ----
 #pragma unroll
@@ -207,8 +339,23 @@ __global__ __launch_bounds__(HEAD_THREADS, 2) void head_bwd_kernel(
       }
     }
 
-    if (next < ntiles) write_dz(buf ^ 1);
+    if (!CE && next < ntiles) write_dz(buf ^ 1);
     buf ^= 1;
+  }
+
+  if (CE) {
+    // one loss atomic per block
+    __shared__ float lred[HEAD_THREADS / 64];
+#pragma unroll
+    for (int off = 32; off; off >>= 1) lsum += __shfl_xor(lsum, off, 64);
+    if (lane == 0) lred[wid] = lsum;
+    __syncthreads();
+    if (t == 0) {
+      float s = 0.f;
+#pragma unroll
+      for (int i = 0; i < HEAD_THREADS / 64; ++i) s += lred[i];
+      if (s != 0.f) atomicAdd(loss, s);
+    }
   }
 
   // flush: accumulator lane (c = l15, q), element r <-> h = base + 4q + r
@@ -226,6 +373,30 @@ __global__ __launch_bounds__(HEAD_THREADS, 2) void head_bwd_kernel(
     }
     if (db != nullptr && wid == 0 && q == 0) atomicAdd(db + l15, accb[0]);
   }
+}
+
+template <int H, bool TR>
+__global__ __launch_bounds__(HEAD_THREADS, 2) void head_bwd_kernel(
+    const bf16raw* __restrict__ dz_out, const bf16raw* __restrict__ w,
+    const bf16raw* __restrict__ y_in, bf16raw* __restrict__ dz_in, float* __restrict__ dw,
+    float* __restrict__ db, int B, int C) {
+  head_tiles<H, TR, false>(dz_out, w, y_in, dz_in, dw, db, B, C, nullptr, nullptr, nullptr,
+                           nullptr, 0.f);
+}
+
+// Head forward + cross-entropy (mean over B) + head backward in one pass:
+// with logits = y_in @ w^T + bias rounded to bf16 (gemm_kernel's EPI_BIAS
+// arithmetic) and dz_out = d loss / d logits as ce_fused produces it,
+//   loss  += sum_b (lse_b - logit_b[t_b]) / B      (the launcher zeroes it)
+//   dz_in, dw, db as head_bwd_kernel; logits_out (nullable) gets the logits.
+template <int H>
+__global__ __launch_bounds__(HEAD_THREADS, 2) void head_ce_kernel(
+    const bf16raw* __restrict__ w, const float* __restrict__ bias,
+    const bf16raw* __restrict__ y_in, const int64_t* __restrict__ tgt,
+    bf16raw* __restrict__ dz_in, float* __restrict__ dw, float* __restrict__ db,
+    float* __restrict__ loss, bf16raw* __restrict__ logits_out, int B, int C, float inv_B) {
+  head_tiles<H, true, true>(nullptr, w, y_in, dz_in, dw, db, B, C, bias, tgt, loss, logits_out,
+                            inv_B);
 }
 
 // 1 when (C, H) is served by the fused kernel
@@ -253,6 +424,33 @@ extern "C" hipError_t launch_head_bwd(const bf16raw* dz_out, const bf16raw* w,
     default: HEAD_LAUNCH(512); break;
   }
 #undef HEAD_LAUNCH
+  HIP_CHECK_LAUNCH();
+  return hipSuccess;
+}
+
+// Same shape range and grid rule as launch_head_bwd.  loss is defined, not
+// accumulated: it is zeroed on the stream first.
+extern "C" hipError_t launch_head_ce(const bf16raw* w, const float* bias, const bf16raw* y_in,
+                                     const int64_t* tgt, bf16raw* dz_in, float* dw, float* db,
+                                     float* loss, bf16raw* logits_out, int B, int C, int H,
+                                     int max_blocks, int num_cus, hipStream_t stream) {
+  if (!head_bwd_supported(C, H) || B < 1) return hipErrorInvalidValue;
+  const int ntiles = (B + head_rows(H) - 1) / head_rows(H);
+  int grid = 2 * (num_cus > 0 ? num_cus : 256);
+  if (max_blocks > 0 && grid > max_blocks) grid = max_blocks;
+  if (grid > ntiles) grid = ntiles;
+  hipError_t err = hipMemsetAsync(loss, 0, sizeof(float), stream);
+  if (err != hipSuccess) return err;
+#define HEAD_CE_LAUNCH(HH)                                                    \
+  head_ce_kernel<HH><<<dim3(grid), dim3(HEAD_THREADS), 0, stream>>>(          \
+      w, bias, y_in, tgt, dz_in, dw, db, loss, logits_out, B, C, 1.0f / B)
+  switch (H) {
+    case 64: HEAD_CE_LAUNCH(64); break;
+    case 128: HEAD_CE_LAUNCH(128); break;
+    case 256: HEAD_CE_LAUNCH(256); break;
+    default: HEAD_CE_LAUNCH(512); break;
+  }
+#undef HEAD_CE_LAUNCH
   HIP_CHECK_LAUNCH();
   return hipSuccess;
 }

@@ -81,7 +81,7 @@ __global__ void ce_fused_wave_kernel(const bf16raw* __restrict__ logits,
 
 extern "C" hipError_t launch_ce_fused(const bf16raw* logits, const int64_t* tgt, float* loss_out,
                                       bf16raw* dlogits, int B, int C, hipStream_t stream) {
-  if (C >= 128 || B <= 2048) {
+  if (C >= 128 || B <= CE_WAVE_MAX_B) {
     int grid = (int)ceil_div_i64(B, 4);
     ce_fused_wave_kernel<<<grid, 256, 0, stream>>>(logits, tgt, loss_out, dlogits, B, C,
                                                    1.0f / B);

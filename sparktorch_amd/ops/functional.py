@@ -9,7 +9,9 @@ backward:
                                  batches: persistent streaming kernel with db
   db = colsum(dz)              — bias_grad
 Layer stacks (hip_mlp_chain) fold the ReLU mask into the consumer's dgrad
-epilogue and run a small classifier head's whole backward in one pass.
+epilogue and run a small classifier head's whole backward in one pass; a
+train step under cross-entropy (mlp_chain_ce_step) also folds the head's
+forward and the loss into that pass.
 
 The CPU fallback keeps identical semantics so the same model code runs in the
 no-GPU sandbox; on a GPU the extension is REQUIRED (ops.ext() raises).
@@ -299,6 +301,98 @@ def hip_mlp_chain(x: torch.Tensor, layers) -> torch.Tensor:
         if relu:
             x = F.relu(x)
     return x
+
+
+# Tests flip this to force forward -> ce_fused -> head backward for the head.
+_HEAD_CE_FUSION = True
+
+
+def _head_ce_ok(ext, w: torch.Tensor) -> bool:
+    return _HEAD_CE_FUSION and _head_bwd_ok(ext, w)
+
+
+def linear_head_ce(y_in, w, bias, target, dw, db=None, want_logits: bool = False,
+                   max_blocks: int = 0):
+    """Training pass of a bias-only head ``y_in @ w^T + bias`` on a ReLU
+    output ``y_in`` under mean cross-entropy against ``target`` (int64), with
+    the loss's upstream gradient fixed at 1.  Returns ``(loss, dz_in,
+    logits)``: the fp32 scalar loss, ``dz_in = (dlogits @ w) * (y_in > 0)``
+    and the bf16 logits (``None`` unless ``want_logits``); accumulates
+    ``dw += dlogits^T @ y_in`` and ``db += colsum(dlogits)`` (fp32, caller
+    zeroes).  One pass over ``y_in`` (head_bwd.hip, head_ce_kernel) where the
+    shape qualifies, else linear_fwd -> ce_fused -> linear_head_bwd."""
+    ext = ops.ext()
+    if _head_ce_ok(ext, w):
+        loss, dz_in, logits = ext.linear_head_ce(y_in, w, bias, target, dw, db, want_logits,
+                                                 max_blocks)
+        return loss, dz_in, (logits if want_logits else None)
+    logits = ext.linear_fwd(y_in, w, bias, False, _LINEAR_STREAM)
+    loss, dlogits = ext.ce_fused(logits, target)
+    dz_in = linear_head_bwd(dlogits, w, y_in, dw, db, max_blocks)
+    return loss, dz_in, (logits if want_logits else None)
+
+
+def _grad_is_direct(p) -> bool:
+    return (p.requires_grad and p.grad is not None and p.grad.dtype == torch.float32
+            and p.grad.is_contiguous() and getattr(p, "_bucket_notify", None) is not None)
+
+
+def mlp_chain_ce_supported(x: torch.Tensor, layers) -> bool:
+    """Can ``mlp_chain_ce_step`` run this stack: a GPU input that needs no
+    gradient, a plain head the one-pass kernel serves on top of a ReLU layer,
+    and every parameter's gradient going straight into its bucket view."""
+    if not (x.is_cuda and not x.requires_grad and len(layers) >= 2):
+        return False
+    if layers[-1][2] or not layers[-2][2]:
+        return False
+    for w, b, _ in layers:
+        if w.dtype != torch.float32 or not _grad_is_direct(w):
+            return False
+        if b is not None and not _grad_is_direct(b):
+            return False
+    w = layers[-1][0]
+    return bool(_HEAD_CE_FUSION and _HEAD_FUSION
+                and ops.ext().head_bwd_supported(w.shape[0], w.shape[1]))
+
+
+@torch.no_grad()
+def mlp_chain_ce_step(x: torch.Tensor, layers, target: torch.Tensor) -> torch.Tensor:
+    """Forward, mean cross-entropy and backward of ``layers`` (as for
+    hip_mlp_chain) in one explicit call: returns the fp32 loss and leaves
+    d loss / d param in every parameter's bucket view, the buckets notified.
+    Not an autograd node — the loss's upstream gradient is 1 by construction,
+    which is what lets the head's forward, the loss and the head's backward
+    share one pass over the last hidden activation (linear_head_ce).  The
+    rest is _MLPChainFn's kernel sequence.  Callers check
+    ``mlp_chain_ce_supported`` first."""
+    ext = ops.ext()
+    if x.dtype != torch.bfloat16:
+        x = x.to(torch.bfloat16)
+    if not x.is_contiguous():
+        x = x.contiguous()
+    x = x.reshape(-1, x.shape[-1])
+    target = target.flatten().long().contiguous()
+    n = len(layers)
+    acts, wbs = [x], []
+    for w, b, relu in layers[:-1]:
+        wbs.append(ext.cast_f32_bf16(w))
+        acts.append(ext.linear_fwd(acts[-1], wbs[-1], b, bool(relu), _LINEAR_STREAM))
+    w, b, _ = layers[-1]
+    loss, dz, _ = linear_head_ce(acts[-1], ext.cast_f32_bf16(w), b, target, w.grad,
+                                 b.grad if b is not None else None)
+    w._bucket_notify()
+    if b is not None:
+        b._bucket_notify()
+    for i in range(n - 2, -1, -1):
+        w, b, _ = layers[i]
+        dz_prev = None
+        if i > 0 and layers[i - 1][2]:
+            dz_prev = ext.linear_dgrad_relu(dz, wbs[i], acts[i], _LINEAR_STREAM)
+        elif i > 0:
+            dz_prev = ext.linear_dgrad(dz, wbs[i], _LINEAR_STREAM)
+        _linear_param_grads(ext, dz, acts[i], w, b, True, b is not None)
+        dz = dz_prev
+    return loss
 
 
 class _Conv2dFn(torch.autograd.Function):

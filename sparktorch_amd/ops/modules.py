@@ -29,6 +29,8 @@ from sparktorch_amd.ops.functional import (
     hip_max_pool2d,
     hip_max_pool2d_nhwc,
     hip_mlp_chain,
+    mlp_chain_ce_step,
+    mlp_chain_ce_supported,
     hip_relu,
     hip_mse,
 )
@@ -321,11 +323,23 @@ class MnistMLPFused(nn.Module):
         self.fc2 = HipLinear(hidden, hidden, activation="relu")
         self.fc3 = HipLinear(hidden, classes, activation=None)
 
+    def _layers(self):
+        return [(fc.weight, fc.bias, fc.activation == "relu")
+                for fc in (self.fc1, self.fc2, self.fc3)]
+
     def forward(self, x: torch.Tensor) -> torch.Tensor:
         # one autograd node for the stack: the backward fuses the ReLU masks
         # into the dgrad epilogues and the fc3 backward into one pass
-        return hip_mlp_chain(x, [(fc.weight, fc.bias, fc.activation == "relu")
-                                 for fc in (self.fc1, self.fc2, self.fc3)])
+        return hip_mlp_chain(x, self._layers())
+
+    def ce_step_supported(self, x: torch.Tensor) -> bool:
+        return mlp_chain_ce_supported(x, self._layers())
+
+    def ce_step(self, x: torch.Tensor, target: torch.Tensor) -> torch.Tensor:
+        """Forward + mean cross-entropy + backward without autograd
+        (mlp_chain_ce_step): returns the loss, gradients land in the bucket
+        views.  Only where ``ce_step_supported(x)``."""
+        return mlp_chain_ce_step(x, self._layers(), target)
 
 
 def convert_model_for_mi355x(model: nn.Module) -> nn.Module:

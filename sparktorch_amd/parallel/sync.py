@@ -133,6 +133,19 @@ class SyncTrainer:
 
     # ------------------------------------------------------------------
     def _forward_backward(self, x: torch.Tensor, y: torch.Tensor) -> torch.Tensor:
+        # A model that offers the explicit forward + cross-entropy + backward
+        # step (MnistMLPFused.ce_step) takes it when the loss is the fused
+        # cross-entropy and every gradient goes straight into its bucket view:
+        # the head's forward, the loss and the head's backward are one kernel.
+        if (
+            self.native
+            and type(self.criterion).__name__ == "HipCrossEntropy"
+            and (not self.compile_mode or self.compile_mode == "hipgraph")
+            and y is not None
+            and hasattr(self.model, "ce_step_supported")
+            and self.model.ce_step_supported(x)
+        ):
+            return self.model.ce_step(x, y)
         pred = self.model(x)
         loss = compute_loss(self.criterion, pred, y)
         loss.backward()
