@@ -20,7 +20,7 @@ OPS_DIR = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(OPS_DIR, "csrc")
 BUILD_DIR = os.path.join(OPS_DIR, "build")
 
-HIP_SOURCES = ["elementwise.hip", "loss.hip", "gemm.hip", "conv.hip", "norm.hip", "conv_nhwc.hip", "conv_implicit.hip", "head_bwd.hip", "linear_wgrad.hip", "sample_gather.hip", "linear_stream.hip"]
+HIP_SOURCES = ["elementwise.hip", "loss.hip", "gemm.hip", "conv.hip", "norm.hip", "conv_nhwc.hip", "conv_implicit.hip", "head_bwd.hip", "linear_wgrad.hip", "sample_gather.hip", "linear_stream.hip", "mlp_predict.hip"]
 CPP_SOURCES = ["bindings.cpp"]
 
 ROCM = os.environ.get("ROCM_PATH", "/opt/rocm")

@@ -60,6 +60,11 @@ hipError_t launch_head_bwd(const bf16raw*, const bf16raw*, const bf16raw*, bf16r
                            float*, int, int, int, int, int, hipStream_t);
 hipError_t launch_head_ce(const bf16raw*, const float*, const bf16raw*, const int64_t*, bf16raw*,
                           float*, float*, float*, bf16raw*, int, int, int, int, int, hipStream_t);
+int mlp_predict_supported(int, const int*, int, int, int64_t);
+int64_t mlp_predict_min_rows();
+hipError_t launch_mlp_predict(const bf16raw*, const bf16raw* const*, const float* const*,
+                              const int*, int, int, int, int64_t, int*, bf16raw*, int, int,
+                              hipStream_t);
 hipError_t launch_bn_stats(const bf16raw*, float*, float*, float*, float*, float*, float*, int,
                            int, int64_t, float, float, int, hipStream_t);
 hipError_t launch_bn_apply(const bf16raw*, const bf16raw*, bf16raw*, const float*, const float*,
@@ -614,6 +619,73 @@ std::tuple<at::Tensor, at::Tensor, at::Tensor> linear_head_ce(
   return {loss, dz_in, logits};
 }
 
+// Whole-MLP inference in one launch (mlp_predict.hip): x through the hidden
+// layers relu(h W^T + b) and the head, to one int32 class id per row (argmax
+// of the bf16 logits) and, when asked, the logits themselves.  `weights` and
+// `biases` list the hidden layers and then the head; a bias may be None.
+bool mlp_predict_ok(int64_t K0, std::vector<int64_t> widths, int64_t C) {
+  if (widths.empty() || widths.size() > 4 || K0 < 1 || K0 >= (1 << 24) || C < 1 || C > (1 << 16))
+    return false;
+  int wv[4];
+  for (size_t i = 0; i < widths.size(); ++i) {
+    if (widths[i] < 1 || widths[i] > (1 << 16)) return false;
+    wv[i] = (int)widths[i];
+  }
+  return mlp_predict_supported((int)K0, wv, (int)widths.size(), (int)C, 1) != 0;
+}
+
+int64_t mlp_predict_min_rows_py() { return mlp_predict_min_rows(); }
+
+std::tuple<at::Tensor, c10::optional<at::Tensor>> mlp_predict(
+    at::Tensor x, std::vector<at::Tensor> weights, std::vector<c10::optional<at::Tensor>> biases,
+    bool want_logits, int64_t max_blocks) {
+  check_gpu_contig(x, at::kBFloat16, "x");
+  TORCH_CHECK(x.dim() == 2, "x must be [M, K0]");
+  TORCH_CHECK(weights.size() >= 2 && weights.size() <= 5,
+              "mlp_predict: one to four hidden layers and a head");
+  TORCH_CHECK(biases.size() == weights.size(), "one bias entry (or None) per layer");
+  const int64_t M = x.size(0), K0 = x.size(1);
+  const int L = (int)weights.size() - 1;
+  const bf16raw* wp[5] = {};
+  const float* bp[5] = {};
+  std::vector<int64_t> widths;
+  int wv[4] = {};
+  int64_t k = K0;
+  bool aligned = aligned16(x);
+  for (int l = 0; l <= L; ++l) {
+    const at::Tensor& w = weights[l];
+    check_gpu_contig(w, at::kBFloat16, "weight");
+    TORCH_CHECK(w.dim() == 2 && w.size(1) == k && w.device() == x.device(),
+                "shape mismatch along the chain at layer ", l);
+    wp[l] = (const bf16raw*)w.data_ptr();
+    aligned = aligned && aligned16(w);
+    if (biases[l].has_value()) {
+      check_gpu_contig(*biases[l], at::kFloat, "bias");
+      TORCH_CHECK(biases[l]->numel() == w.size(0) && biases[l]->device() == x.device(),
+                  "bias does not match its layer");
+      bp[l] = biases[l]->data_ptr<float>();
+      aligned = aligned && aligned16(*biases[l]);
+    }
+    k = w.size(0);
+    if (l < L) {
+      widths.push_back(k);
+      wv[l] = (int)(k < (1 << 16) ? k : 0);
+    }
+  }
+  const int64_t C = k;
+  TORCH_CHECK(mlp_predict_ok(K0, widths, C) &&
+                  mlp_predict_supported((int)K0, wv, L, (int)C, M) != 0,
+              "mlp_predict: unsupported (K0, widths, C, M); use the per-layer route");
+  TORCH_CHECK(aligned, "mlp_predict wants 16-byte aligned operands");
+  auto classes = at::empty({M}, x.options().dtype(at::kInt));
+  c10::optional<at::Tensor> logits;
+  if (want_logits) logits = at::empty({M, C}, x.options());
+  CHECK_HIP(launch_mlp_predict((const bf16raw*)x.data_ptr(), wp, bp, wv, L, (int)K0, (int)C, M,
+                               classes.data_ptr<int>(),
+                               want_logits ? (bf16raw*)logits->data_ptr() : nullptr,
+                               (int)max_blocks, head_num_cus(), cur_stream()));
+  return {classes, logits};
+}
 
 // tiny-output wgrad: batched outer product instead of a ~98%-dead MFMA tile
 static bool small_wgrad_path(int64_t M, int64_t N, int64_t K) {
@@ -1245,6 +1317,14 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "head forward + cross-entropy + one-pass head backward: (loss, dz_in, logits)",
         py::arg("y_in"), py::arg("w"), py::arg("bias"), py::arg("target"), py::arg("dw"),
         py::arg("db"), py::arg("want_logits") = false, py::arg("max_blocks") = 0);
+  m.def("mlp_predict_supported", &mlp_predict_ok,
+        "does the one-launch MLP inference kernel serve (K0, hidden widths, C)");
+  m.def("mlp_predict_min_rows", &mlp_predict_min_rows_py,
+        "rows from which MnistMLPFused.forward takes the one-launch inference kernel");
+  m.def("mlp_predict", &mlp_predict,
+        "hidden layers + head + argmax in one launch: (classes int32, logits or None)",
+        py::arg("x"), py::arg("weights"), py::arg("biases"), py::arg("want_logits") = false,
+        py::arg("max_blocks") = 0);
   m.def("linear_wgrad_stream_supported", &linear_wgrad_stream_ok,
         "is (No, Ki) at batch B routed to the batch-streaming wgrad");
   m.def("linear_wgrad_stream_can_run", &linear_wgrad_stream_runs,

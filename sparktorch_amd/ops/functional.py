@@ -303,6 +303,64 @@ def hip_mlp_chain(x: torch.Tensor, layers) -> torch.Tensor:
     return x
 
 
+# Tests flip this to force the per-layer chain + argmax for hip_mlp_predict.
+_PREDICT_FUSION = True
+
+
+def _mlp_predict_ok(x: torch.Tensor, layers) -> bool:
+    """Does the one-launch inference kernel (mlp_predict.hip) serve this
+    chain: a 2-D GPU input, ReLU hidden layers of a supported width, a plain
+    head of 2..16 classes."""
+    if not (_PREDICT_FUSION and x.is_cuda and x.dim() == 2 and x.shape[0] >= 1):
+        return False
+    if not 2 <= len(layers) <= 5:
+        return False
+    if layers[-1][2] or not all(r for _, _, r in layers[:-1]):
+        return False
+    k = x.shape[1]
+    for w, b, _ in layers:
+        if w.dim() != 2 or w.shape[1] != k or w.dtype not in (torch.float32, torch.bfloat16):
+            return False
+        if b is not None and b.dtype != torch.float32:
+            return False
+        k = w.shape[0]
+    widths = [int(w.shape[0]) for w, _, _ in layers[:-1]]
+    return bool(ops.ext().mlp_predict_supported(int(x.shape[1]), widths, int(k)))
+
+
+def mlp_predict_min_rows() -> int:
+    """Rows from which ``MnistMLPFused.forward`` routes an inference batch
+    through the one-launch kernel (measured: profiles/mlp_predict.md)."""
+    return int(ops.ext().mlp_predict_min_rows())
+
+
+@torch.no_grad()
+def hip_mlp_predict(x: torch.Tensor, layers, want_logits: bool = False, max_blocks: int = 0):
+    """Inference through ``layers`` (as for hip_mlp_chain): returns
+    ``(classes, logits)`` with ``classes`` the int32 argmax of each row's
+    logits (lowest index on ties, as np.argmax) and ``logits`` the chain's
+    output, or ``None`` unless ``want_logits``.  GPU: one launch
+    (mlp_predict.hip) that reads x once and keeps the hidden activations in
+    LDS, where it serves the chain; the logits are bit-identical to
+    hip_mlp_chain's.  Anything else (CPU, an unsupported width or class
+    count, a hidden layer without ReLU, a head with one, more than four
+    hidden layers, misaligned operands) runs hip_mlp_chain and torch.argmax."""
+    if x.is_cuda and x.dim() == 2 and _mlp_predict_ok(x, layers):
+        ext = ops.ext()
+        xb = x if x.dtype == torch.bfloat16 else x.to(torch.bfloat16)
+        if not xb.is_contiguous():
+            xb = xb.contiguous()
+        ws = [(ext.cast_f32_bf16(w) if w.dtype == torch.float32 else w).contiguous()
+              for w, _, _ in layers]
+        bs = [None if b is None else b.detach().contiguous() for _, b, _ in layers]
+        if all(t.data_ptr() % 16 == 0 for t in [xb] + ws + [b for b in bs if b is not None]):
+            classes, logits = ext.mlp_predict(xb, ws, bs, bool(want_logits), int(max_blocks))
+            return classes, (logits if want_logits else None)
+    logits = hip_mlp_chain(x, layers)
+    classes = torch.argmax(logits.float(), dim=-1).to(torch.int32)
+    return classes, (logits if want_logits else None)
+
+
 # Tests flip this to force forward -> ce_fused -> head backward for the head.
 _HEAD_CE_FUSION = True
 

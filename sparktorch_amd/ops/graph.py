@@ -9,9 +9,20 @@ entire cost at batch-1 in the reference design.
 
 from __future__ import annotations
 
-from typing import Optional
+from typing import Callable, Optional
 
 import torch
+
+
+def class_id_call(model) -> Optional[Callable[[torch.Tensor], torch.Tensor]]:
+    """``model.predict_classes`` where the model offers it for a multi-output
+    net (one int32 class id per row, the argmax of its logits), else None.
+    Callers that only want the argmax capture it in place of ``model(x)`` and
+    copy back 4 bytes a row."""
+    fn = getattr(model, "predict_classes", None)
+    if not callable(fn) or int(getattr(model, "num_classes", 2)) < 2:
+        return None
+    return fn
 
 
 class GraphedForward:
@@ -19,11 +30,15 @@ class GraphedForward:
 
     Inputs shorter than ``batch_size`` are padded (rows beyond the real count
     are sliced off the output), so ONE graph serves every batch including the
-    ragged tail.
+    ragged tail.  ``call``, when given, is captured in place of ``model(x)``:
+    any callable of the device batch that returns one tensor with a leading
+    batch dimension (e.g. ``model.predict_classes``).
     """
 
-    def __init__(self, model: torch.nn.Module, device: str = "cuda:0", batch_size: int = 8192):
+    def __init__(self, model: torch.nn.Module, device: str = "cuda:0", batch_size: int = 8192,
+                 call: Optional[Callable[[torch.Tensor], torch.Tensor]] = None):
         self.model = model.to(device).eval()
+        self._call = call if call is not None else self.model
         self.device = device
         self.batch_size = batch_size
         self._graph: Optional[torch.cuda.CUDAGraph] = None
@@ -37,11 +52,11 @@ class GraphedForward:
         s.wait_stream(torch.cuda.current_stream())
         with torch.cuda.stream(s), torch.no_grad():
             for _ in range(2):
-                out = self.model(x)
+                out = self._call(x)
         torch.cuda.current_stream().wait_stream(s)
         g = torch.cuda.CUDAGraph()
         with torch.cuda.graph(g), torch.no_grad():
-            out = self.model(x)
+            out = self._call(x)
         self._graph = g
         self._static_in = x
         self._static_out = out

@@ -15,6 +15,7 @@ from typing import Optional
 import torch
 import torch.nn as nn
 
+from sparktorch_amd.ops import functional as F_ops
 from sparktorch_amd.ops.functional import (
     hip_add_relu,
     hip_batch_norm2d,
@@ -29,6 +30,7 @@ from sparktorch_amd.ops.functional import (
     hip_max_pool2d,
     hip_max_pool2d_nhwc,
     hip_mlp_chain,
+    hip_mlp_predict,
     mlp_chain_ce_step,
     mlp_chain_ce_supported,
     hip_relu,
@@ -328,9 +330,26 @@ class MnistMLPFused(nn.Module):
                 for fc in (self.fc1, self.fc2, self.fc3)]
 
     def forward(self, x: torch.Tensor) -> torch.Tensor:
+        layers = self._layers()
+        # inference on a big enough batch: the whole chain in one launch, the
+        # hidden activations never leave LDS; the logits are bit-identical
+        if (not self.training and not torch.is_grad_enabled() and x.is_cuda and x.dim() == 2
+                and F_ops._PREDICT_FUSION and F_ops._mlp_predict_ok(x, layers)
+                and x.shape[0] >= F_ops.mlp_predict_min_rows()):
+            return F_ops.hip_mlp_predict(x, layers, want_logits=True)[1]
         # one autograd node for the stack: the backward fuses the ReLU masks
         # into the dgrad epilogues and the fc3 backward into one pass
-        return hip_mlp_chain(x, self._layers())
+        return hip_mlp_chain(x, layers)
+
+    @property
+    def num_classes(self) -> int:
+        return self.fc3.out_features
+
+    def predict_classes(self, x: torch.Tensor) -> torch.Tensor:
+        """int32 class id per row: the argmax of ``forward(x)``'s logits
+        (lowest index on ties), without materialising them where the
+        one-launch inference kernel serves the chain."""
+        return hip_mlp_predict(x, self._layers())[0]
 
     def ce_step_supported(self, x: torch.Tensor) -> bool:
         return mlp_chain_ce_supported(x, self._layers())

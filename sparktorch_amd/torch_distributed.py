@@ -108,10 +108,15 @@ class SparkTorchModel(
         model.eval()
         bs = int(self.getOrDefault(self.batchSize))
         runner = None
+        ids_only = False
         if device.startswith("cuda"):
-            from sparktorch_amd.ops.graph import GraphedForward
+            from sparktorch_amd.ops.graph import GraphedForward, class_id_call
 
-            runner = GraphedForward(model, device=device, batch_size=bs)
+            # only the argmax is wanted: capture the model's class-id call and
+            # copy back 4 bytes a row instead of the logits
+            call = None if use_vector else class_id_call(model)
+            ids_only = call is not None
+            runner = GraphedForward(model, device=device, batch_size=bs, call=call)
         out: List[Any] = []
         with torch.no_grad():
             for s in range(0, len(feats), bs):
@@ -120,7 +125,13 @@ class SparkTorchModel(
                     pred = runner(xb)
                 else:
                     pred = model(xb.to(device))
-                pred = pred.detach().cpu().numpy()
+                pred = pred.detach()
+                if ids_only:
+                    out.extend(pred.cpu().numpy().astype(np.float64).tolist())
+                    continue
+                if pred.dtype in (torch.bfloat16, torch.float16):
+                    pred = pred.float()  # numpy has no bf16; the widening is exact
+                pred = pred.cpu().numpy()
                 if use_vector:
                     out.extend([row.astype(np.float64) for row in pred])
                 else:
@@ -175,7 +186,10 @@ class SparkTorchModel(
             with _torch.no_grad():
                 for s in range(0, len(rows), bs):
                     xb = _torch.from_numpy(feats[s : s + bs]).to(dev)
-                    pred = model(xb).detach().cpu().numpy()
+                    pred = model(xb).detach()
+                    if pred.dtype in (_torch.bfloat16, _torch.float16):
+                        pred = pred.float()  # numpy has no bf16; the widening is exact
+                    pred = pred.cpu().numpy()
                     for j, row in enumerate(rows[s : s + bs]):
                         if use_vector:
                             yield row + (Vectors.dense(pred[j].astype(_np.float64).flatten()),)
