@@ -27,6 +27,13 @@ ROCM = os.environ.get("ROCM_PATH", "/opt/rocm")
 ARCH = os.environ.get("PYTORCH_ROCM_ARCH", "gfx950")
 
 
+def build_dependencies():
+    """Every file whose edit must rebuild the extension: the translation
+    units and every header in csrc (a header is included, never listed)."""
+    headers = sorted(f for f in os.listdir(CSRC) if f.endswith(".h"))
+    return [os.path.join(CSRC, s) for s in HIP_SOURCES + CPP_SOURCES + headers]
+
+
 def _ext_path() -> str:
     suffix = sysconfig.get_config_var("EXT_SUFFIX") or ".so"
     return os.path.join(OPS_DIR, "_sparkhip" + suffix)
@@ -67,10 +74,7 @@ def build_extension(
     in_tree = out is None
     out = out or _ext_path()
     build_dir = build_dir or BUILD_DIR
-    srcs = [os.path.join(CSRC, s) for s in HIP_SOURCES + CPP_SOURCES] + [
-        os.path.join(CSRC, "common.h")
-    ]
-    if in_tree and not force and not _needs_build(out, srcs):
+    if in_tree and not force and not _needs_build(out, build_dependencies()):
         return out
 
     os.makedirs(build_dir, exist_ok=True)

@@ -7,9 +7,10 @@
 // tensor xP [B][H+2P][W+2P][CI]:
 //
 //   * every 8-element (16 B) k-granule lies inside one (kh,kw) ci-run
-//     (CI % 8 == 0), so clean k-chunks stage by async global_load_lds with
-//     the usual row-XOR slot swizzle; the K tail (K % BKT != 0) takes a
-//     zero-filling register fallback into the same swizzled image;
+//     (CI % 8 == 0), so clean k-chunks stage by async global_load_lds into
+//     mfma_tile.h's k-major image (the patch address per row is this file's
+//     own); the K tail (K % BKT != 0) takes a zero-filling register fallback
+//     into the same image;
 //   * the pad ring is materialized once per tensor (pad_nhwc) — no patch
 //     address is ever out of bounds, no branches in the hot stage;
 //   * stride-1 dgrad IS the forward kernel: dx = conv_s1(pad(dz, KH-1-p),
@@ -25,11 +26,9 @@
 // CI % 16 == 0, CO % 8 == 0; wmat column-padded to a multiple of 64.
 // Everything else keeps the explicit im2col path.
 
-#include "common.h"
+#include "mfma_tile.h"
 
 #define IC_LDS_PAD 8
-
-typedef shortx8 cfrag_t;
 
 __device__ __forceinline__ int ic_swz(int row, int col) {
   return col ^ (((row >> 4) & 3) << 3);
@@ -190,9 +189,7 @@ __device__ __forceinline__ void stage_patch_glds(const bf16raw* __restrict__ xP,
     int ci = r2 - kw * g.CI;
     const bf16raw* gp =
         xP + (((int64_t)b * g.Hp + oh * g.SH + kh) * g.Wp + ow * g.SW + kw) * g.CI + ci;
-    __builtin_amdgcn_global_load_lds(
-        (const __attribute__((address_space(1))) unsigned int*)gp,
-        (__attribute__((address_space(3))) unsigned int*)(lds + c * CH_ROWS * BKT), 16, 0, 0);
+    mt_glds16(gp, lds + c * CH_ROWS * BKT);
   }
 }
 
@@ -265,12 +262,17 @@ __device__ __forceinline__ void stage_w_glds(const bf16raw* __restrict__ src,
     if (grow >= N) grow = N - 1;
     int sslot = slot ^ (row & (SLOTS - 1));
     const bf16raw* g = src + (int64_t)grow * srow + kt + sslot * 8;
-    __builtin_amdgcn_global_load_lds(
-        (const __attribute__((address_space(1))) unsigned int*)g,
-        (__attribute__((address_space(3))) unsigned int*)(lds + c * CH_ROWS * BKT), 16, 0, 0);
+    mt_glds16(g, lds + c * CH_ROWS * BKT);
   }
 }
 
+// The forward kernel's staging loops, fragment reads, MFMA step and epilogue
+// follow mfma_tile.h's image, k-packing and rounding order but are written out
+// here: through mt_ld_frag / mt_mma_tile / mt_epi_slice and a callable-address
+// DMA loop every forward kernel's machine code changed, and no kernel tool
+// times this file (profiles/tile_refactor.md).  As written the file compiles
+// to the parent's code.
+//
 // NFR = active 16-column output fragments per wave (4 = the full 64-wide
 // sub-tile; 1 serves N <= 16 shapes — e.g. a CI=16 dgrad — without
 // issuing 75% dead MFMAs).
@@ -286,13 +288,8 @@ __global__ __launch_bounds__(WR * WC * 64, 2) void conv_implicit_fwd_kernel(
   __shared__ bf16raw As[2][BMt * BKT];
   __shared__ bf16raw Bs[2][BNt * BKT];
 
-  // XCD-aware bijective block swizzle (same as gemm.hip)
   const int gx = gridDim.x;
-  int nwg = gx * gridDim.y;
-  int orig = blockIdx.y * gx + blockIdx.x;
-  int q = nwg >> 3, rr = nwg & 7;
-  int wg = ((orig & 7) < rr ? (orig & 7) * (q + 1) : rr * (q + 1) + ((orig & 7) - rr) * q) +
-           (orig >> 3);
+  const int wg = mt_xcd_block_id(gx);
   const int m0 = (wg % gx) * BMt;
   const int n0 = (wg / gx) * BNt;
 
@@ -322,18 +319,18 @@ __global__ __launch_bounds__(WR * WC * 64, 2) void conv_implicit_fwd_kernel(
 
 #pragma unroll
     for (int sub = 0; sub < SUBS; ++sub) {
-      cfrag_t a[4], b[NFR];
+      mt_frag_t a[4], b[NFR];
 #pragma unroll
       for (int mi = 0; mi < 4; ++mi) {
         int row = wr * 64 + mi * 16 + l15;
         int kq = kg + sub * 4;
-        a[mi] = *(const cfrag_t*)&As[buf][row * BKT + ((kq ^ (row & (SLOTS - 1))) << 3)];
+        a[mi] = *(const mt_frag_t*)&As[buf][row * BKT + ((kq ^ (row & (SLOTS - 1))) << 3)];
       }
 #pragma unroll
       for (int ni = 0; ni < NFR; ++ni) {
         int rowb = wc * 64 + ni * 16 + l15;
         int kq = kg + sub * 4;
-        b[ni] = *(const cfrag_t*)&Bs[buf][rowb * BKT + ((kq ^ (rowb & (SLOTS - 1))) << 3)];
+        b[ni] = *(const mt_frag_t*)&Bs[buf][rowb * BKT + ((kq ^ (rowb & (SLOTS - 1))) << 3)];
       }
 #pragma unroll
       for (int mi = 0; mi < 4; ++mi)
@@ -349,12 +346,12 @@ __global__ __launch_bounds__(WR * WC * 64, 2) void conv_implicit_fwd_kernel(
 #undef IC_STAGE
 
   // bf16 epilogue via per-wave LDS transpose (one contiguous 16 B store per
-  // lane) — same layout trick as gemm.hip's bf16 epilogue.  N % 8 == 0.
+  // lane), mt_epi_slice's layout and rounding order with the stride-2 row
+  // compaction and the N / NFR column guards added.  N % 8 == 0.
   const int m_base = m0 + wr * 64;
   const int n_base = n0 + wc * 64;
   __syncthreads();
-  constexpr int EPAD = 68;
-  float* ep = (float*)&As[0][0] + wid * 16 * EPAD;
+  float* ep = (float*)&As[0][0] + wid * 16 * MT_EPAD;
   const int orow = lane >> 2;
   const int oct = lane & 3;
 #pragma unroll
@@ -362,7 +359,7 @@ __global__ __launch_bounds__(WR * WC * 64, 2) void conv_implicit_fwd_kernel(
 #pragma unroll
     for (int ni = 0; ni < NFR; ++ni)
 #pragma unroll
-      for (int r = 0; r < 4; ++r) ep[(kg * 4 + r) * EPAD + ni * 16 + l15] = acc[mi][ni][r];
+      for (int r = 0; r < 4; ++r) ep[(kg * 4 + r) * MT_EPAD + ni * 16 + l15] = acc[mi][ni][r];
     __builtin_amdgcn_s_waitcnt(0);
     int m = m_base + mi * 16 + orow;
     int64_t mout = m;
@@ -380,7 +377,7 @@ __global__ __launch_bounds__(WR * WC * 64, 2) void conv_implicit_fwd_kernel(
         int n = n_base + c0;
         if (c0 < NFR * 16 && n < N) {
           alignas(16) short outp[8];
-          const float* src = ep + orow * EPAD + c0;
+          const float* src = ep + orow * MT_EPAD + c0;
 #pragma unroll
           for (int j = 0; j < 8; ++j) {
             float val = src[j];
@@ -554,11 +551,7 @@ __global__ __launch_bounds__(256, 2) void conv_implicit_wgrad_kernel(
   __shared__ bf16raw Bs[BNt * LP];
 
   const int gx = gridDim.x;
-  int nwg = gx * gridDim.y;
-  int orig = blockIdx.y * gx + blockIdx.x;
-  int q = nwg >> 3, rr = nwg & 7;
-  int wg = ((orig & 7) < rr ? (orig & 7) * (q + 1) : rr * (q + 1) + ((orig & 7) - rr) * q) +
-           (orig >> 3);
+  const int wg = mt_xcd_block_id(gx);
   const int m0 = (wg % gx) * BMt;
   const int n0 = (wg / gx) * BNt;
 
@@ -601,16 +594,16 @@ __global__ __launch_bounds__(256, 2) void conv_implicit_wgrad_kernel(
 
 #pragma unroll
     for (int sub = 0; sub < 2; ++sub) {
-      cfrag_t a[MFR], b[4];
+      mt_frag_t a[MFR], b[4];
 #pragma unroll
       for (int mi = 0; mi < MFR; ++mi) {
         int row = wr * 64 + mi * 16 + l15;
-        a[mi] = *(const cfrag_t*)&As[row * LP + sub * 32 + ic_swz(row, kg * 8)];
+        a[mi] = *(const mt_frag_t*)&As[row * LP + sub * 32 + ic_swz(row, kg * 8)];
       }
 #pragma unroll
       for (int ni = 0; ni < 4; ++ni) {
         int rowb = wc * 64 + ni * 16 + l15;
-        b[ni] = *(const cfrag_t*)&Bs[rowb * LP + sub * 32 + ic_swz(rowb, kg * 8)];
+        b[ni] = *(const mt_frag_t*)&Bs[rowb * LP + sub * 32 + ic_swz(rowb, kg * 8)];
       }
 #pragma unroll
       for (int mi = 0; mi < MFR; ++mi)

@@ -13,10 +13,10 @@
 //
 // Staging (the performance-critical part; every choice here is measured —
 // see profiles/bench_resnet18_optimization_log.md):
-//   * k-contiguous operands (AG/BG): async global_load_lds DMA into a
-//     pad-free LDS image whose 16B k-slots are XOR-swizzled by row (lane-
-//     linear for the DMA, bank-spread for ds_read_b128 fragment reads);
-//     boundary slabs take a vectorized swizzled fallback.
+//   * k-contiguous operands (AG/BG): async global_load_lds DMA into
+//     mfma_tile.h's k-major LDS image (its header describes the image and
+//     the k-packing of a fragment); boundary slabs take a vectorized
+//     swizzled fallback.
 //   * transposing operands (wgrad — the reduction runs over the outer
 //     stride of both matrices): T14 register pipeline — hold the slab in
 //     registers, write LDS after the barrier, issue the next slab's loads
@@ -43,29 +43,13 @@
 // (ones_row).  The XCD-aware block swizzle keeps an output tile's operand
 // rows inside one XCD's L2.
 
-#include "common.h"
+#include "mfma_tile.h"
 
 #define BM 128
 #define BN 128
 #define BK 32
 #define LDS_PAD 8          // 8 bf16 = 16 B: rows stay 16-byte aligned
 #define LDSK (BK + LDS_PAD)
-
-// EPI codes
-#define EPI_F32 0        // fp32 store (atomicAdd when SPLITK)
-#define EPI_BF16 1       // bf16 store
-#define EPI_BIAS 2       // bf16 store, + bias[n]
-#define EPI_BIAS_RELU 3  // bf16 store, + bias[n], relu
-#define EPI_RELU 4       // bf16 store, relu (no bias)
-#define EPI_F32_SLAB 5   // fp32 per-slice slab store (split-K without atomics;
-                         // a separate reduce kernel combines the slabs —
-                         // guide §5 "splitk-seam": slab reducer beats an
-                         // fp32-atomicAdd accumulator)
-#define EPI_BF16_MASK 6  // bf16 store, zeroed where mask[m][n] <= 0 (mask: bf16
-                         // [M][N], same layout as C) — dgrad with the upstream
-                         // ReLU backward folded in
-
-typedef shortx8 frag_t;  // 8 bf16 (4 VGPRs)
 
 // Stage a [ROWS x BK] tile (ROWS=128) into LDS laid out [ROWS][LDSK].
 // Logical element (r, k) comes from src[(row0+r)*srow + (kt+k)*skol].
@@ -74,7 +58,6 @@ typedef shortx8 frag_t;  // 8 bf16 (4 VGPRs)
 //   else if srow==1 (row-contiguous): thread covers 16 consecutive rows at
 //     fixed k (vectorized along rows, strided LDS column writes).
 //   else: scalar element loop.
-#define BF16_ONE ((bf16raw)0x3F80)
 
 // Granule swizzle for the PADDED LDS images: XOR the 8-element (16 B)
 // granule index of a 32-k half by row bits >= 4.  The srow-staging write
@@ -105,9 +88,9 @@ __device__ __forceinline__ void stage_tile(const void* __restrict__ src, bf16raw
     bf16raw* d1 = lds + r * LDSTRIDE + swz_col(r, k0 + 8);
     if (ones_row >= 0 && gr == ones_row) {
 #pragma unroll
-      for (int j = 0; j < 8; ++j) d0[j] = (kt + k0 + j < kmax) ? BF16_ONE : (bf16raw)0;
+      for (int j = 0; j < 8; ++j) d0[j] = (kt + k0 + j < kmax) ? MT_BF16_ONE : (bf16raw)0;
 #pragma unroll
-      for (int j = 0; j < 8; ++j) d1[j] = (kt + k0 + 8 + j < kmax) ? BF16_ONE : (bf16raw)0;
+      for (int j = 0; j < 8; ++j) d1[j] = (kt + k0 + 8 + j < kmax) ? MT_BF16_ONE : (bf16raw)0;
     } else if (gr < mem_rows) {
       const char* base = (const char*)src + (int64_t)gr * srow * (SRC_F32 ? 4 : 2);
       int krem = kmax - kt - k0;  // how many of our 16 k are in range
@@ -175,7 +158,7 @@ __device__ __forceinline__ void stage_tile(const void* __restrict__ src, bf16raw
           int r = r0 + j;
           bf16raw v = 0;
           if (ones_row >= 0 && row0 + r == ones_row)
-            v = BF16_ONE;
+            v = MT_BF16_ONE;
           else if (j < mem_rem)  // row0 + r < mem_rows
             v = SRC_F32 ? f32_to_bf16(((const float*)base)[row0 + r])
                         : ((const bf16raw*)base)[row0 + r];
@@ -196,7 +179,7 @@ __device__ __forceinline__ void stage_tile(const void* __restrict__ src, bf16raw
       int gr = row0 + r, gk = kt + k;
       bf16raw v = 0;
       if (ones_row >= 0 && gr == ones_row && gk < kmax) {
-        v = BF16_ONE;
+        v = MT_BF16_ONE;
       } else if (gr < mem_rows && gk < kmax) {
         const char* p = (const char*)src + ((int64_t)gr * srow + (int64_t)gk * skol) * (SRC_F32 ? 4 : 2);
         v = SRC_F32 ? f32_to_bf16(*(const float*)p) : *(const bf16raw*)p;
@@ -224,7 +207,7 @@ __device__ __forceinline__ void stage_load(const void* __restrict__ src, int row
     int gr = row0 + r;
     if (ones_row >= 0 && gr == ones_row) {
 #pragma unroll
-      for (int j = 0; j < 16; ++j) regs[j] = (kt + k0 + j < kmax) ? BF16_ONE : (bf16raw)0;
+      for (int j = 0; j < 16; ++j) regs[j] = (kt + k0 + j < kmax) ? MT_BF16_ONE : (bf16raw)0;
     } else if (gr < mem_rows) {
       const char* base = (const char*)src + (int64_t)gr * srow * (SRC_F32 ? 4 : 2);
       int krem = kmax - kt - k0;
@@ -281,7 +264,7 @@ __device__ __forceinline__ void stage_load(const void* __restrict__ src, int row
         for (int j = 0; j < 16; ++j) {
           bf16raw v = 0;
           if (ones_row >= 0 && row0 + r0 + j == ones_row)
-            v = BF16_ONE;
+            v = MT_BF16_ONE;
           else if (j < mem_rem)
             v = SRC_F32 ? f32_to_bf16(((const float*)base)[row0 + r0 + j])
                         : ((const bf16raw*)base)[row0 + r0 + j];
@@ -301,7 +284,7 @@ __device__ __forceinline__ void stage_load(const void* __restrict__ src, int row
       int gr = row0 + r, gk = kt + k;
       bf16raw v = 0;
       if (ones_row >= 0 && gr == ones_row && gk < kmax) {
-        v = BF16_ONE;
+        v = MT_BF16_ONE;
       } else if (gr < mem_rows && gk < kmax) {
         const char* p =
             (const char*)src + ((int64_t)gr * srow + (int64_t)gk * skol) * (SRC_F32 ? 4 : 2);
@@ -336,38 +319,11 @@ __device__ __forceinline__ void stage_write(bf16raw* __restrict__ lds, int64_t s
   }
 }
 
-// ---------------------------------------------------------------------------
-// Direct global->LDS staging (glds) for the k-contiguous A operand.  The LDS
-// image is pad-free [ROWS][BKT] bf16 with the 16-byte k-slot of each row
-// XOR-swizzled by (row & (SLOTS-1)) — lane-linear for the DMA (dest is
-// wave-uniform base + lane*16; guide §5 "Async global->LDS"), bank-spread
-// for the ds_read_b128 fragment reads.  The swizzle permutes 16B pieces
-// within one 128B line of the source row, so global coalescing is kept.
-// ---------------------------------------------------------------------------
-
-template <int ROWS, int BKT>
-__device__ __forceinline__ void stage_glds(const bf16raw* __restrict__ src,
-                                           bf16raw* __restrict__ lds, int row0, int64_t sam,
-                                           int kt) {
-  constexpr int SLOTS = BKT / 8;       // 16B slots per LDS row
-  constexpr int CH_ROWS = 64 / SLOTS;  // rows per 1KB wave chunk
-  constexpr int NCHUNK = ROWS / CH_ROWS;
-  const int lane = threadIdx.x & 63;
-  const int wid = threadIdx.x >> 6;
-  const int r_in = lane / SLOTS;
-  const int slot = lane % SLOTS;
-#pragma unroll
-  for (int c = wid; c < NCHUNK; c += 4) {
-    int row = c * CH_ROWS + r_in;
-    int sslot = slot ^ (row & (SLOTS - 1));
-    const bf16raw* g = src + (int64_t)(row0 + row) * sam + kt + sslot * 8;
-    __builtin_amdgcn_global_load_lds(
-        (const __attribute__((address_space(1))) unsigned int*)g,
-        (__attribute__((address_space(3))) unsigned int*)(lds + c * CH_ROWS * BKT), 16, 0, 0);
-  }
-}
-
-// boundary-slab fallback writing the SAME swizzled image with zero fill.
+// k-contiguous operands go global->LDS by DMA (mt_dma_kmajor) into
+// mfma_tile.h's k-major image.  Boundary slabs: a fallback writing the SAME
+// image with zero fill.  It is not mt_fill_kmajor: K here need not be a
+// multiple of 8, so a 16 B slot can straddle kmax and is then filled by
+// element.
 // Vectorized: AG implies a k-contiguous source, so full granules move as
 // shortx8 (the K<BKT degenerate shapes — e.g. a K=32 dgrad — run this every
 // slab, and the original per-element version was the whole kernel's cost).
@@ -427,15 +383,8 @@ __global__ __launch_bounds__(WR * WC * 64, 2) void gemm_kernel(const void* __res
   __shared__ bf16raw As[NBUF][AG ? (BMt * BKT) : (BMt * LP)];
   __shared__ bf16raw Bs[NBUF][BG ? (BROWS * BKT) : (BROWS * LP)];
 
-  // bijective XCD-aware swizzle of the flattened block id (guide §5.5 T1):
-  // consecutive output tiles land on one XCD so shared operand rows stay in
-  // that XCD's L2.
   const int gx = gridDim.x;
-  int nwg = gx * gridDim.y;
-  int orig = blockIdx.y * gx + blockIdx.x;
-  int q = nwg >> 3, rr = nwg & 7;
-  int wg = ((orig & 7) < rr ? (orig & 7) * (q + 1) : rr * (q + 1) + ((orig & 7) - rr) * q) +
-           (orig >> 3);
+  const int wg = mt_xcd_block_id(gx);
   const int m0 = (wg % gx) * BMt;
   const int n0 = (wg / gx) * BNt;
 
@@ -461,13 +410,15 @@ __global__ __launch_bounds__(WR * WC * 64, 2) void gemm_kernel(const void* __res
 #define STAGE_SLAB(bufi, kt)                                                               \
   do {                                                                                     \
     if (a_rows_full && (kt) + BKT <= k_end)                                                \
-      stage_glds<BMt, BKT>((const bf16raw*)Ap, As[bufi], m0, sam, kt);                     \
+      mt_dma_kmajor<4, BMt, BKT, false>((const bf16raw*)Ap, As[bufi], m0, BMt, sam, kt,    \
+                                        wid, lane);                                        \
     else                                                                                   \
       stage_swz_fallback<BMt, BKT>((const bf16raw*)Ap, As[bufi], m0, M, kt, k_end, sam);   \
     /* B staged TRANSPOSED: LDS row = n, col = k -> srow := sbn, skol := sbk */            \
     if (BG) {                                                                              \
       if (n0 + BROWS <= N && (kt) + BKT <= k_end)                                          \
-        stage_glds<BROWS, BKT>((const bf16raw*)Bp, Bs[1 && (bufi)], n0, sbn, kt);          \
+        mt_dma_kmajor<4, BROWS, BKT, false>((const bf16raw*)Bp, Bs[1 && (bufi)], n0,       \
+                                            BROWS, sbn, kt, wid, lane);                    \
       else                                                                                 \
         stage_swz_fallback<BROWS, BKT>((const bf16raw*)Bp, Bs[1 && (bufi)], n0, N, kt,     \
                                        k_end, sbn);                                        \
@@ -487,26 +438,21 @@ __global__ __launch_bounds__(WR * WC * 64, 2) void gemm_kernel(const void* __res
 
 #pragma unroll
       for (int sub = 0; sub < SUBS; ++sub) {
-        frag_t a[4], b[4];
+        mt_frag_t a[4], b[4];
 #pragma unroll
         for (int mi = 0; mi < 4; ++mi) {
           int row = wr * 64 + mi * 16 + l15;
           int kq = kg + sub * 4;
-          a[mi] = *(const frag_t*)&As[buf][row * BKT + (((kq) ^ (row & (SLOTS - 1))) << 3)];
+          a[mi] = mt_ld_frag<BKT, SLOTS - 1>(As[buf], row, kq);
         }
 #pragma unroll
         for (int ni = 0; ni < 4; ++ni) {
           int rowb = wc * 64 + ni * 16 + l15;
           int kq = kg + sub * 4;
-          b[ni] = BG ? *(const frag_t*)&Bs[buf][rowb * BKT + (((kq) ^ (rowb & (SLOTS - 1))) << 3)]
-                     : *(const frag_t*)&Bs[buf][rowb * LP + sub * 32 + swz_col(rowb, kg * 8)];
+          b[ni] = BG ? mt_ld_frag<BKT, SLOTS - 1>(Bs[buf], rowb, kq)
+                     : *(const mt_frag_t*)&Bs[buf][rowb * LP + sub * 32 + swz_col(rowb, kg * 8)];
         }
-#pragma unroll
-        for (int mi = 0; mi < 4; ++mi)
-#pragma unroll
-          for (int ni = 0; ni < 4; ++ni)
-            acc[mi][ni] =
-                __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[mi], b[ni], acc[mi][ni], 0, 0, 0);
+        mt_mma_tile(acc, a, b);
       }
 
       __syncthreads();
@@ -574,17 +520,20 @@ __global__ __launch_bounds__(WR * WC * 64, 2) void gemm_kernel(const void* __res
 
 #pragma unroll
       for (int sub = 0; sub < SUBS; ++sub) {
-        frag_t a[4], b[4];
+        mt_frag_t a[4], b[4];
 #pragma unroll
         for (int mi = 0; mi < 4; ++mi) {
           int row = wr * 64 + mi * 16 + l15;
-          a[mi] = *(const frag_t*)&As[0][row * LP + sub * 32 + swz_col(row, kg * 8)];
+          a[mi] = *(const mt_frag_t*)&As[0][row * LP + sub * 32 + swz_col(row, kg * 8)];
         }
 #pragma unroll
         for (int ni = 0; ni < 4; ++ni) {
           int rowb = wc * 64 + ni * 16 + l15;
-          b[ni] = *(const frag_t*)&Bs[0][rowb * LP + sub * 32 + swz_col(rowb, kg * 8)];
+          b[ni] = *(const mt_frag_t*)&Bs[0][rowb * LP + sub * 32 + swz_col(rowb, kg * 8)];
         }
+        // not mt_mma_tile: through the helper this path's instruction schedule
+        // changed and the split-K wgrad shapes measured up to 1 % slower
+        // (profiles/tile_refactor.md)
 #pragma unroll
         for (int mi = 0; mi < 4; ++mi)
 #pragma unroll
@@ -596,59 +545,24 @@ __global__ __launch_bounds__(WR * WC * 64, 2) void gemm_kernel(const void* __res
 #undef LOAD_SLAB
   }
 
-  // epilogue.  bf16 outputs go through a per-wave LDS transpose so each
-  // lane stores one contiguous 16 B octet (scalar 2 B stores measured the
-  // C-write path at ~2.3 TB/s vs ~4.4 for reads); the MFMA fragment layout
-  // (col = lane&15, row = 4*(lane>>4)+reg) cannot produce contiguous
-  // per-lane stores directly.  fp32/split-K keeps the scalar path (atomics).
+  // epilogue: bf16 outputs through mfma_tile.h's per-wave LDS transpose;
+  // fp32 / split-K keeps the scalar path (atomics), and so do bf16 tiles
+  // whose 64 columns do not all exist or are not 16 B aligned.
   const int m_base = m0 + wr * 64;
   const int n_base = n0 + wc * 64;
   if (EPI != EPI_F32 && EPI != EPI_F32_SLAB && (N & 7) == 0 && n_base + 64 <= N) {
     // all waves must be past their final fragment reads before the scratch
     // overwrites the staging images (the T14 loop has no trailing barrier)
     __syncthreads();
-    // per-wave [16][68] fp32 scratch inside the (now idle) LDS staging
-    // buffers: As holds 4x(16x68x4B) for the 4-wave tiles; the 8-wave wide
-    // tile needs 34.8 KB and uses Bs (36.9 KB there)
-    constexpr int EPAD = 68;
-    float* ep = (THREADS == 512 ? (float*)&Bs[0][0] : (float*)&As[0][0]) + wid * 16 * EPAD;
-    const int orow = lane >> 2;          // 0..15 output row of the mi-slice
-    const int oct = lane & 3;            // which 16-col half-octet pair
+    // the scratch lies inside the (now idle) staging buffers: As holds it for
+    // the 4-wave tiles; the 8-wave wide tile needs 34.8 KB and uses Bs
+    // (36.9 KB there)
+    float* ep = (THREADS == 512 ? (float*)&Bs[0][0] : (float*)&As[0][0]) + wid * MT_EP_FLOATS;
 #pragma unroll
     for (int mi = 0; mi < 4; ++mi) {
-      // mask octets are fetched before the fragment goes through the LDS
-      // scratch so the global load overlaps the transpose
-      shortx8 mk[2] = {};
-      if (EPI == EPI_BF16_MASK && m_base + mi * 16 + orow < M) {
-        const bf16raw* mp = mask + (int64_t)(m_base + mi * 16 + orow) * N + n_base + oct * 16;
-        mk[0] = *(const shortx8*)mp;
-        mk[1] = *(const shortx8*)(mp + 8);
-      }
-#pragma unroll
-      for (int ni = 0; ni < 4; ++ni)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) ep[(kg * 4 + r) * EPAD + ni * 16 + l15] = acc[mi][ni][r];
-      __builtin_amdgcn_s_waitcnt(0);  // lgkm: own-wave LDS writes visible
-      int m = m_base + mi * 16 + orow;
-      if (m < M) {
-#pragma unroll
-        for (int h = 0; h < 2; ++h) {
-          int c0 = oct * 16 + h * 8;
-          int n = n_base + c0;
-          alignas(16) short outp[8];
-          const float* src = ep + orow * EPAD + c0;
-#pragma unroll
-          for (int j = 0; j < 8; ++j) {
-            float val = src[j];
-            if (EPI == EPI_BIAS || EPI == EPI_BIAS_RELU) val += bias[n + j];
-            if (EPI == EPI_BIAS_RELU || EPI == EPI_RELU) val = fmaxf(val, 0.f);
-            outp[j] = (short)f32_to_bf16(val);
-            if (EPI == EPI_BF16_MASK && !(bf16_to_f32((bf16raw)mk[h][j]) > 0.f)) outp[j] = 0;
-          }
-          *(shortx8*)(Cb + (int64_t)m * N + n) = *(const shortx8*)outp;
-        }
-      }
-      __builtin_amdgcn_s_waitcnt(0);  // all lanes done reading before reuse
+      const int m = m_base + mi * 16 + (lane >> 2);
+      mt_epi_slice<EPI>(ep, acc[mi], lane, l15, kg, m < M, m, N, n_base, Cb, bias,
+                                  mask);
     }
     return;
   }

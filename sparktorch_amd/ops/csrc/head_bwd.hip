@@ -12,7 +12,8 @@
 // Persistent blocks stride over ROWS-row tiles of y_in.  A tile is staged by
 // async global->LDS DMA (double-buffered: tile t+1 is in flight while tile t
 // is consumed; one barrier per tile) into a pad-free row-major image whose
-// 16 B slots are XOR-swizzled by row.  The image is used twice:
+// 16 B slots are XOR-swizzled by row (mfma_tile.h's k-major image, one slab as
+// wide as H).  The image is used twice:
 //   * dgrad computes dz_in^T = w^T[H,C] x dz_out^T[C,rows] so a lane's
 //     accumulators are consecutive h of ONE row; two MFMAs whose M-rows are
 //     interleaved in groups of four give each lane 8 consecutive h = one
@@ -32,54 +33,31 @@
 //
 // head_ce_kernel runs the same tile loop for a train step under mean
 // cross-entropy: it needs no dz_out from memory.  Once a y_in tile is in LDS
-// it computes the tile's logits from that image (one wave per 16 rows, w as
-// a second set of register fragments), applies loss.hip's softmax / loss
-// arithmetic per row and writes the bf16 dlogits into the [rows][16] image
-// itself; an LDS-only barrier publishes the image and the two stages above
-// run unchanged.  The head's forward, the loss and the head's backward then
-// read y_in once and the logits never reach HBM (profiles/head_ce.md).
+// it computes the tile's logits from that image (mfma_tile.h's small-head
+// forward: one wave per 16 rows, w as a second set of register fragments),
+// applies loss.hip's softmax / loss arithmetic per row and writes the bf16
+// dlogits into the [rows][16] image itself; an LDS-only barrier publishes the
+// image and the two stages above run unchanged.  The head's forward, the
+// loss and the head's backward then read y_in once and the logits never reach
+// HBM (profiles/head_ce.md).
 
-#include "common.h"
-
-typedef shortx8 hfrag_t;  // 8 bf16 (4 VGPRs)
+#include "mfma_tile.h"
 
 #define HEAD_THREADS 256
 #define HEAD_CPAD 16  // class dim padded to 16 in the dz_out image
 
 __host__ __device__ constexpr int head_rows(int H) { return H <= 256 ? 64 : 32; }
 
-template <bool TR>
-__device__ __forceinline__ hfrag_t head_tr_frag(const bf16raw* __restrict__ img, int stride,
-                                                int xm, int rb, int q, int l15, int col0) {
-  // fragment value i <-> tile row rb + (i/4)*16 + q*4 + (i%4), column
-  // col0 + l15; the same row order is used for both MFMA operands
-  hfrag_t f;
-  if (TR) {
-    const int col = col0 + 4 * (l15 & 3);
-#pragma unroll
-    for (int jh = 0; jh < 2; ++jh) {
-      const int row = rb + jh * 16 + q * 4 + (l15 >> 2);
-      const bf16raw* p = img + row * stride + ((((col >> 3) ^ (row & xm)) << 3) | (col & 7));
-      shortx4 v = __builtin_amdgcn_ds_read_tr16_b64_v4i16(
-          (__attribute__((address_space(3))) shortx4*)p);
-#pragma unroll
-      for (int j = 0; j < 4; ++j) f[jh * 4 + j] = v[j];
-    }
-  } else {
-    const int col = col0 + l15;
-#pragma unroll
-    for (int i = 0; i < 8; ++i) {
-      const int row = rb + (i >> 2) * 16 + q * 4 + (i & 3);
-      f[i] = (short)img[row * stride + ((((col >> 3) ^ (row & xm)) << 3) | (col & 7))];
-    }
-  }
-  return f;
-}
+// slot ^= row & XM of the y_in image (0: the dz image is not swizzled)
+template <int XM>
+struct head_key {
+  static __device__ __forceinline__ int key(int row) { return row & XM; }
+};
 
 // Tile loop shared by head_bwd_kernel (CE = false: the dz_out image is staged
 // from global memory) and head_ce_kernel (CE = true: the image is computed
 // from the resident y_in tile; dz_out is unused).
-template <int H, bool TR, bool CE>
+template <int H, bool CE>
 __device__ __forceinline__ void head_tiles(
     const bf16raw* __restrict__ dz_out, const bf16raw* __restrict__ w,
     const bf16raw* __restrict__ y_in, bf16raw* __restrict__ dz_in, float* __restrict__ dw,
@@ -106,7 +84,7 @@ __device__ __forceinline__ void head_tiles(
 
   // w fragments (dgrad A operand, M = h, K = class padded to 32).  M-row m of
   // fragment e of a group maps to h = group*32 + (m/4)*8 + e*4 + (m%4).
-  hfrag_t wf[PW][2];
+  mt_frag_t wf[PW][2];
 #pragma unroll
   for (int pi = 0; pi < PW; ++pi) {
     const int p = wid + pi * 4;
@@ -120,25 +98,20 @@ __device__ __forceinline__ void head_tiles(
       }
     }
   }
-  hfrag_t ones;
+  mt_frag_t ones;
 #pragma unroll
-  for (int i = 0; i < 8; ++i) ones[i] = (short)0x3F80;
+  for (int i = 0; i < 8; ++i) ones[i] = (short)MT_BF16_ONE;
 
   floatx4 accw[PW][2] = {};
   floatx4 accb = {0.f, 0.f, 0.f, 0.f};
 
-  // CE: w again as the forward's B operand (N = class, k ascending as in
-  // gemm_kernel: lane (class l15, q) holds k = ks*32 + q*8 .. +7), the
-  // lane's bias, next tile's targets and the block's loss
-  hfrag_t wk[CE ? H / 32 : 1];
+  // CE: w again as the forward's B operand, the lane's bias, next tile's
+  // targets and the block's loss
+  mt_frag_t wk[H / 32];
   float bias_c = 0.f, lsum = 0.f;
   int tg[4] = {0, 0, 0, 0};
   if (CE) {
-#pragma unroll
-    for (int ks = 0; ks < H / 32; ++ks) {
-      wk[ks] = hfrag_t{};
-      if (l15 < C) wk[ks] = *(const hfrag_t*)&w[l15 * H + ks * 32 + q * 8];
-    }
+    mt_head_w_frags(wk, w, H, C, l15, q);
     if (bias != nullptr && l15 < C) bias_c = bias[l15];
   }
   // targets of the rows whose logits this lane receives (wave wid owns tile
@@ -175,9 +148,7 @@ __device__ __forceinline__ void head_tiles(
       int64_t gr = (int64_t)tile * ROWS + row;
       if (gr > B - 1) gr = B - 1;
       const bf16raw* g = y_in + gr * H + slot * 8;
-      __builtin_amdgcn_global_load_lds(
-          (const __attribute__((address_space(1))) unsigned int*)g,
-          (__attribute__((address_space(3))) unsigned int*)(ys[b] + c * 512), 16, 0, 0);
+      mt_glds16(g, ys[b] + c * 512);
     }
   };
 
@@ -196,7 +167,7 @@ __device__ __forceinline__ void head_tiles(
     // tile's images are complete and every wave is done with the other pair
     // (CE says so itself: each wave's DMA of this tile has landed)
     if (CE)
-      asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)\n\ts_barrier" ::: "memory");
+      mt_wait_barrier<0>();
     else
       __syncthreads();
     const int next = tile + gridDim.x;
@@ -213,12 +184,8 @@ __device__ __forceinline__ void head_tiles(
       constexpr bool EARLY = H <= 256;
       const bool fwd_wave = wid < ROWS / 16;  // one 16-row fragment per wave
       const int arow = wid * 16 + l15;
-      hfrag_t ay[H / 32];
-      if (EARLY && fwd_wave) {
-#pragma unroll
-        for (int ks = 0; ks < H / 32; ++ks)
-          ay[ks] = *(const hfrag_t*)&yb[arow * H + (((ks * 4 + q) ^ (arow & XM)) << 3)];
-      }
+      mt_frag_t ay[H / 32];
+      if (EARLY && fwd_wave) mt_head_a_frags<H / 32, H, XM>(ay, yb, arow, q);
       if (next < ntiles) {
         dma_y(buf ^ 1, next);
         load_tgt(next);
@@ -226,13 +193,8 @@ __device__ __forceinline__ void head_tiles(
       // ---- logits, softmax, loss and the dz image of this tile ----
       if (fwd_wave) {
 #pragma clang fp reassociate(off)  // the class sums keep loss.hip's order
-        floatx4 lg = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-        for (int ks = 0; ks < H / 32; ++ks) {
-          if (!EARLY)
-            ay[ks] = *(const hfrag_t*)&yb[arow * H + (((ks * 4 + q) ^ (arow & XM)) << 3)];
-          lg = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ay[ks], wk[ks], lg, 0, 0, 0);
-        }
+        const floatx4 lg = EARLY ? mt_head_logits(ay, wk)
+                                 : mt_head_logits<H / 32, H, XM>(wk, yb, arow, H, q);
         // lane (class l15, q), element r <-> tile row wid*16 + q*4 + r.  The
         // per-row arithmetic is loss.hip's; RG rows go side by side so their
         // lane exchanges overlap (H = 512 has the registers for one).
@@ -287,7 +249,7 @@ __device__ __forceinline__ void head_tiles(
         }
       }
       // publish the dz image; the next tile's DMA stays in flight
-      asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
+      mt_lds_barrier();
     } else if (next < ntiles) {
       load_dz(next);
       dma_y(buf ^ 1, next);
@@ -297,8 +259,8 @@ __device__ __forceinline__ void head_tiles(
 #pragma unroll
     for (int rf = 0; rf < ROWS / 16; ++rf) {
       const int row = rf * 16 + l15;
-      hfrag_t bz = {};
-      if (q < 2) bz = *(const hfrag_t*)&zb[row * HEAD_CPAD + q * 8];
+      mt_frag_t bz = {};
+      if (q < 2) bz = mt_ld_frag<HEAD_CPAD, 0>(zb, row, q);
 #pragma unroll
       for (int pi = 0; pi < PW; ++pi) {
         const int p = wid + pi * 4;
@@ -307,7 +269,7 @@ __device__ __forceinline__ void head_tiles(
           floatx4 a0 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wf[pi][0], bz, z, 0, 0, 0);
           floatx4 a1 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wf[pi][1], bz, z, 0, 0, 0);
           const int slot = p * 4 + q;
-          const shortx8 mk = *(const shortx8*)&yb[row * H + ((slot ^ (row & XM)) << 3)];
+          const shortx8 mk = mt_ld_frag<H, XM>(yb, row, slot);
           shortx8 out;
 #pragma unroll
           for (int j = 0; j < 4; ++j) {
@@ -323,7 +285,9 @@ __device__ __forceinline__ void head_tiles(
     // ---- wgrad + bias grad ----
 #pragma unroll
     for (int ks = 0; ks < ROWS / 32; ++ks) {
-      const hfrag_t bz = head_tr_frag<TR>(zb, HEAD_CPAD, 0, ks * 32, q, l15, 0);
+      // fragment value i <-> tile row ks*32 + (i/4)*16 + q*4 + (i%4), the same
+      // row order for both operands
+      const mt_frag_t bz = mt_tr_frag<HEAD_CPAD, 4, 16, head_key<0>>(zb, ks * 32, q, l15, 0);
       if (wid == 0)
         accb = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ones, bz, accb, 0, 0, 0);
 #pragma unroll
@@ -332,7 +296,8 @@ __device__ __forceinline__ void head_tiles(
         if (p < NP) {
 #pragma unroll
           for (int e = 0; e < 2; ++e) {
-            const hfrag_t ay = head_tr_frag<TR>(yb, H, XM, ks * 32, q, l15, p * 32 + e * 16);
+            const mt_frag_t ay =
+                mt_tr_frag<H, 4, 16, head_key<XM>>(yb, ks * 32, q, l15, p * 32 + e * 16);
             accw[pi][e] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ay, bz, accw[pi][e], 0, 0, 0);
           }
         }
@@ -375,13 +340,13 @@ __device__ __forceinline__ void head_tiles(
   }
 }
 
-template <int H, bool TR>
+template <int H>
 __global__ __launch_bounds__(HEAD_THREADS, 2) void head_bwd_kernel(
     const bf16raw* __restrict__ dz_out, const bf16raw* __restrict__ w,
     const bf16raw* __restrict__ y_in, bf16raw* __restrict__ dz_in, float* __restrict__ dw,
     float* __restrict__ db, int B, int C) {
-  head_tiles<H, TR, false>(dz_out, w, y_in, dz_in, dw, db, B, C, nullptr, nullptr, nullptr,
-                           nullptr, 0.f);
+  head_tiles<H, false>(dz_out, w, y_in, dz_in, dw, db, B, C, nullptr, nullptr, nullptr, nullptr,
+                       0.f);
 }
 
 // Head forward + cross-entropy (mean over B) + head backward in one pass:
@@ -395,8 +360,8 @@ __global__ __launch_bounds__(HEAD_THREADS, 2) void head_ce_kernel(
     const bf16raw* __restrict__ y_in, const int64_t* __restrict__ tgt,
     bf16raw* __restrict__ dz_in, float* __restrict__ dw, float* __restrict__ db,
     float* __restrict__ loss, bf16raw* __restrict__ logits_out, int B, int C, float inv_B) {
-  head_tiles<H, true, true>(nullptr, w, y_in, dz_in, dw, db, B, C, bias, tgt, loss, logits_out,
-                            inv_B);
+  head_tiles<H, true>(nullptr, w, y_in, dz_in, dw, db, B, C, bias, tgt, loss, logits_out,
+                      inv_B);
 }
 
 // 1 when (C, H) is served by the fused kernel
@@ -414,9 +379,9 @@ extern "C" hipError_t launch_head_bwd(const bf16raw* dz_out, const bf16raw* w,
   int grid = 2 * (num_cus > 0 ? num_cus : 256);
   if (max_blocks > 0 && grid > max_blocks) grid = max_blocks;
   if (grid > ntiles) grid = ntiles;
-#define HEAD_LAUNCH(HH)                                                                     \
-  head_bwd_kernel<HH, true><<<dim3(grid), dim3(HEAD_THREADS), 0, stream>>>(dz_out, w, y_in, \
-                                                                            dz_in, dw, db, B, C)
+#define HEAD_LAUNCH(HH)                                                                      \
+  head_bwd_kernel<HH><<<dim3(grid), dim3(HEAD_THREADS), 0, stream>>>(dz_out, w, y_in, dz_in, dw, \
+                                                                      db, B, C)
   switch (H) {
     case 64: HEAD_LAUNCH(64); break;
     case 128: HEAD_LAUNCH(128); break;

@@ -31,9 +31,7 @@
 // the last column tile are clamped to the row's last 16 B slot and are never
 // flushed (MFMA output columns are independent).
 
-#include "common.h"
-
-typedef shortx8 lwg_frag_t;  // 8 bf16 (4 VGPRs)
+#include "mfma_tile.h"
 
 #define LWG_THREADS 256
 #define LWG_ROWS 32    // batch rows per tile = one 16x16x32 k-step
@@ -44,28 +42,18 @@ typedef shortx8 lwg_frag_t;  // 8 bf16 (4 VGPRs)
 // 8 rows x 32 B (one 16-column fragment = an aligned slot pair per row); the
 // key moves the 8 rows' pairs onto 8 distinct 32 B bank groups.
 template <int SLOTS>
-__device__ __forceinline__ int lwg_key(int row) {
-  return SLOTS >= 16 ? ((row & 7) << 1) : (((row >> 1) & 3) << 1);
-}
+struct lwg_key {
+  static __device__ __forceinline__ int key(int row) {
+    return SLOTS >= 16 ? ((row & 7) << 1) : (((row >> 1) & 3) << 1);
+  }
+};
 
 // fragment value i <-> tile row (i/4)*16 + q*4 + (i%4), column col0 + l15
 // (the same row order for both operands, so the k pairing is consistent)
 template <int SLOTS>
-__device__ __forceinline__ lwg_frag_t lwg_tr_frag(const bf16raw* __restrict__ img, int q, int l15,
-                                                  int col0) {
-  lwg_frag_t f;
-  const int col = col0 + 4 * (l15 & 3);
-#pragma unroll
-  for (int jh = 0; jh < 2; ++jh) {
-    const int row = jh * 16 + q * 4 + (l15 >> 2);
-    const bf16raw* p =
-        img + row * (SLOTS * 8) + ((((col >> 3) ^ lwg_key<SLOTS>(row)) << 3) | (col & 7));
-    shortx4 v = __builtin_amdgcn_ds_read_tr16_b64_v4i16(
-        (__attribute__((address_space(3))) shortx4*)p);
-#pragma unroll
-    for (int j = 0; j < 4; ++j) f[jh * 4 + j] = v[j];
-  }
-  return f;
+__device__ __forceinline__ mt_frag_t lwg_tr_frag(const bf16raw* __restrict__ img, int q, int l15,
+                                                 int col0) {
+  return mt_tr_frag<SLOTS * 8, 4, 16, lwg_key<SLOTS>>(img, 0, q, l15, col0);
 }
 
 // MF: 16-row dW fragments per wave (No = 64 * MF); NF: 16-column fragments
@@ -119,9 +107,9 @@ __global__ __launch_bounds__(LWG_THREADS, 2) void linear_wgrad_kernel(
   constexpr int ZRPC = 64 / ZSLOTS, XRPC = 64 / XSLOTS;
   static_assert((4 * ZRPC) % 8 == 0 && (4 * XRPC) % 8 == 0, "key must not depend on the chunk");
   const int zr0 = wid * ZRPC + lane / ZSLOTS;
-  const unsigned zoff = zr0 * NO + (((lane % ZSLOTS) ^ lwg_key<ZSLOTS>(zr0)) << 3);
+  const unsigned zoff = zr0 * NO + (((lane % ZSLOTS) ^ lwg_key<ZSLOTS>::key(zr0)) << 3);
   const int xr0 = wid * XRPC + lane / XSLOTS;
-  int xgs = slot0 + ((lane % XSLOTS) ^ lwg_key<XSLOTS>(xr0));
+  int xgs = slot0 + ((lane % XSLOTS) ^ lwg_key<XSLOTS>::key(xr0));
   if (xgs > kslots - 1) xgs = kslots - 1;
   const unsigned xoff = xr0 * Ki + xgs * 8;
 
@@ -130,29 +118,25 @@ __global__ __launch_bounds__(LWG_THREADS, 2) void linear_wgrad_kernel(
 #pragma unroll
     for (int i = 0; i < ZCH / 4; ++i) {
       const bf16raw* g = dz + (row0 + i * 4 * ZRPC) * NO;
-      __builtin_amdgcn_global_load_lds(
-          (const __attribute__((address_space(1))) unsigned int*)(g + zoff),
-          (__attribute__((address_space(3))) unsigned int*)(zn + (wid + 4 * i) * 512), 16, 0, 0);
+      mt_glds16(g + zoff, zn + (wid + 4 * i) * 512);
     }
 #pragma unroll
     for (int i = 0; i < XCH / 4; ++i) {
       const bf16raw* g = x + (row0 + i * 4 * XRPC) * Ki;
-      __builtin_amdgcn_global_load_lds(
-          (const __attribute__((address_space(1))) unsigned int*)(g + xoff),
-          (__attribute__((address_space(3))) unsigned int*)(xn + (wid + 4 * i) * 512), 16, 0, 0);
+      mt_glds16(g + xoff, xn + (wid + 4 * i) * 512);
     }
   };
 
-  lwg_frag_t ones;
+  mt_frag_t ones;
 #pragma unroll
-  for (int i = 0; i < 8; ++i) ones[i] = (short)0x3F80;
+  for (int i = 0; i < 8; ++i) ones[i] = (short)MT_BF16_ONE;
 
   floatx4 acc[MF][NF] = {};
   floatx4 accb[MF] = {};
   const bool do_db = db != nullptr && ct == 0;
 
   auto mma = [&](const bf16raw* zb, const bf16raw* xb) {
-    lwg_frag_t az[MF];
+    mt_frag_t az[MF];
 #pragma unroll
     for (int a = 0; a < MF; ++a)
       az[a] = lwg_tr_frag<ZSLOTS>(zb, q, l15, (wid * MF + a) * 16);
@@ -163,7 +147,7 @@ __global__ __launch_bounds__(LWG_THREADS, 2) void linear_wgrad_kernel(
     }
 #pragma unroll
     for (int f = 0; f < NF; ++f) {
-      const lwg_frag_t bx = lwg_tr_frag<XSLOTS>(xb, q, l15, f * 16);
+      const mt_frag_t bx = lwg_tr_frag<XSLOTS>(xb, q, l15, f * 16);
 #pragma unroll
       for (int a = 0; a < MF; ++a)
         acc[a][f] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(az[a], bx, acc[a][f], 0, 0, 0);
@@ -230,7 +214,7 @@ __global__ __launch_bounds__(LWG_THREADS, 2) void linear_wgrad_kernel(
       for (int j = 0; j < MF; ++j) {
         const int u = t + j * LWG_THREADS;
         const int row = u / ZSLOTS;
-        const int slot = (u % ZSLOTS) ^ lwg_key<ZSLOTS>(row);
+        const int slot = (u % ZSLOTS) ^ lwg_key<ZSLOTS>::key(row);
         shortx8 v = {};
         if (row0 + row < B) v = *(const shortx8*)(dz + (row0 + row) * NO + slot * 8);
         *(shortx8*)(zs0 + u * 8) = v;
@@ -239,7 +223,7 @@ __global__ __launch_bounds__(LWG_THREADS, 2) void linear_wgrad_kernel(
       for (int j = 0; j < LWG_ROWS * XSLOTS / LWG_THREADS; ++j) {
         const int u = t + j * LWG_THREADS;
         const int row = u / XSLOTS;
-        int gs = slot0 + ((u % XSLOTS) ^ lwg_key<XSLOTS>(row));
+        int gs = slot0 + ((u % XSLOTS) ^ lwg_key<XSLOTS>::key(row));
         if (gs > kslots - 1) gs = kslots - 1;
         shortx8 v = {};
         if (row0 + row < B) v = *(const shortx8*)(x + (row0 + row) * Ki + gs * 8);

@@ -11,24 +11,24 @@
 //   * A persistent block of 8 waves (2 x 4, a 64x64 sub-tile each, as
 //     linear_stream.hip) owns 128-row tiles and ALL columns of every layer.
 //   * Layer 1 is linear_stream_kernel's forward k-loop in arithmetic: A and W
-//     go global->LDS by DMA in 32-deep slabs, one fp32 accumulator per
-//     output, K ascending in 32-wide MFMA steps, K tail and rows past M
-//     zero-filled.  With 158 KB of LDS a CU holds ONE block, so the rings are
-//     deeper than linear_stream's: A (from HBM) runs four slabs ahead through
-//     a ring of five, W (from L2) two ahead through a ring of three, and a
-//     counted vmcnt wait leaves everything newer than the next step's slabs
-//     in flight across the step's one barrier.
-//   * The epilogue (+bias, relu, bf16 rounding: linear_stream's arithmetic)
+//     go global->LDS by DMA in 32-deep slabs (mfma_tile.h's k-major image),
+//     one fp32 accumulator per output, K ascending in 32-wide MFMA steps, K
+//     tail and rows past M zero-filled.  With 158 KB of LDS a CU holds ONE
+//     block, so the rings are deeper than linear_stream's: A (from HBM) runs
+//     four slabs ahead through a ring of five, W (from L2) two ahead through
+//     a ring of three, and a counted vmcnt wait leaves everything newer than
+//     the next step's slabs in flight across the step's one barrier.
+//   * The epilogue (+bias, relu, bf16 rounding, in mfma_tile.h's order)
 //     stores into an LDS activation image [128][256] whose 16 B k-slots are
-//     XOR-swizzled by row: a ds_read_b128 of it IS the next layer's A
-//     fragment (the layout of the staged slabs and of head_bwd.hip's ys).
+//     XOR-swizzled by row: a ds_read_b128 of it (mt_ld_frag) IS the next
+//     layer's A fragment.
 //   * Layers 2..L read A from the image (all of K resident) and stream W_l
 //     through the same W ring; the accumulators hold the whole output, so
 //     after the k-loop's closing barrier the epilogue overwrites the image in
 //     place.
-//   * The head is head_ce_kernel's forward stage: one wave per 16 rows, w as
-//     k-ascending B fragments in registers, lane (class l15, q) receives the
-//     logits of rows q*4 .. q*4+3, f32_to_bf16(lg + bias).
+//   * The head is mfma_tile.h's small-head forward: one wave per 16 rows, w
+//     as k-ascending B fragments in registers, lane (class l15, q) receives
+//     the logits of rows q*4 .. q*4+3, f32_to_bf16(lg + bias).
 //   * argmax over the C live lanes by 16-wide shuffles of an integer key made
 //     from the bf16 bits (sign-magnitude -> ordered, NaN forced to the top)
 //     with 15 - class in the low bits: the lowest index wins ties and the
@@ -40,17 +40,14 @@
 //     so the epilogue issues no vector-memory load that would have to wait
 //     behind those DMAs.
 //
-// Every fragment carries gemm.hip's k-packing (lane group kg holds
-// k = 8kg .. 8kg+7 of the 32-wide step) and K ascends, so the logits are
-// bit-identical to the per-layer linear_fwd chain.
+// Every fragment carries mfma_tile.h's k-packing and K ascends, so the
+// logits are bit-identical to the per-layer linear_fwd chain.
 //
 // LDS: 40 KB A ring + 48 KB W ring + 64 KB image + 4 KB biases = 156 KB, one
 // block per CU.  Widths 64 / 128 / 192 leave wave columns idle in that layer
 // (they still help staging).
 
-#include "common.h"
-
-typedef shortx8 mp_frag_t;  // 8 bf16 (4 VGPRs)
+#include "mfma_tile.h"
 
 #define MP_THREADS 512
 #define MP_WAVES 8
@@ -72,52 +69,6 @@ struct MlpPredictArgs {
   bf16raw* logits;  // nullptr = not wanted
 };
 
-// ---- k-contiguous operand: image [ROWS][BKT], slot ^= row & (SLOTS - 1) ----
-// (linear_stream.hip's ls_dma_kmajor / ls_fill_kmajor)
-
-// Source rows row0 .. row0 + nrows - 1 must exist; nrows >= 64.  Image rows
-// at or past nrows get copies of valid rows (never read), so that every wave
-// issues the same ROWS * BKT * 2 / 1024 / MP_WAVES instructions whatever
-// nrows is: the counted waits rely on it.
-template <int ROWS, int BKT>
-__device__ __forceinline__ void mp_dma_kmajor(const bf16raw* __restrict__ src,
-                                              bf16raw* __restrict__ lds, int64_t row0, int nrows,
-                                              int ld, int kt, int wid, int lane) {
-  constexpr int SLOTS = BKT / 8;       // 16 B slots per image row
-  constexpr int CH_ROWS = 64 / SLOTS;  // rows per 1 KB wave chunk
-  constexpr int NCHUNK = ROWS / CH_ROWS;
-  const int r_in = lane / SLOTS;
-  const int slot = lane % SLOTS;
-#pragma unroll
-  for (int c0 = 0; c0 < NCHUNK; c0 += MP_WAVES) {
-    const int c = c0 + wid;
-    const int row = c * CH_ROWS + r_in;
-    const int srow = row < nrows ? row : (row & 63);
-    const int sslot = slot ^ (row & (SLOTS - 1));
-    const bf16raw* g = src + (row0 + srow) * ld + kt + sslot * 8;
-    __builtin_amdgcn_global_load_lds(
-        (const __attribute__((address_space(1))) unsigned int*)g,
-        (__attribute__((address_space(3))) unsigned int*)(lds + c * CH_ROWS * BKT), 16, 0, 0);
-  }
-}
-
-// the same image with zero fill: rows at or past rmax, k at or past kmax
-// (K is a multiple of 8, so a slot is wholly inside or wholly outside)
-template <int ROWS, int BKT>
-__device__ __forceinline__ void mp_fill_kmajor(const bf16raw* __restrict__ src,
-                                               bf16raw* __restrict__ lds, int64_t row0,
-                                               int64_t rmax, int ld, int kt, int kmax, int t) {
-  constexpr int SLOTS = BKT / 8;
-#pragma unroll
-  for (int u = t; u < ROWS * SLOTS; u += MP_THREADS) {
-    const int row = u / SLOTS;
-    const int k = kt + (((u % SLOTS) ^ (row & (SLOTS - 1))) << 3);
-    shortx8 v = {};
-    if (row0 + row < rmax && k < kmax) v = *(const shortx8*)(src + (row0 + row) * ld + k);
-    *(shortx8*)(lds + u * 8) = v;
-  }
-}
-
 // DMA instructions a wave issues per slab
 #define MP_A_DMA (MP_BM * MP_BK * 2 / 1024 / MP_WAVES)
 #define MP_W_DMA (MP_BN * MP_BK * 2 / 1024 / MP_WAVES)
@@ -129,11 +80,11 @@ __device__ __forceinline__ void mp_fill_kmajor(const bf16raw* __restrict__ src,
 __device__ __forceinline__ void mp_publish(int newer) {
   static_assert(MP_A_DMA == 1 && MP_W_DMA == 2, "the cases below are written for these counts");
   switch (newer) {
-    case 4: asm volatile("s_waitcnt vmcnt(4) lgkmcnt(0)\n\ts_barrier" ::: "memory"); break;
-    case 3: asm volatile("s_waitcnt vmcnt(3) lgkmcnt(0)\n\ts_barrier" ::: "memory"); break;
-    case 2: asm volatile("s_waitcnt vmcnt(2) lgkmcnt(0)\n\ts_barrier" ::: "memory"); break;
-    case 1: asm volatile("s_waitcnt vmcnt(1) lgkmcnt(0)\n\ts_barrier" ::: "memory"); break;
-    default: asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)\n\ts_barrier" ::: "memory"); break;
+    case 4: mt_wait_barrier<4>(); break;
+    case 3: mt_wait_barrier<3>(); break;
+    case 2: mt_wait_barrier<2>(); break;
+    case 1: mt_wait_barrier<1>(); break;
+    default: mt_wait_barrier<0>(); break;
   }
 }
 
@@ -144,8 +95,7 @@ __global__ __launch_bounds__(MP_THREADS, 2) void mlp_predict_kernel(const MlpPre
   constexpr int IMG_XM = 15;  // image slot ^= row & 15 (32 slots a row)
   constexpr int IMG_EL = MP_BM * MP_BN;
   constexpr int SB_EL = MP_MAX_HIDDEN * MP_BN * 2;  // hidden biases, in bf16 units
-  // one array, as linear_stream.hip: the A ring, the W ring, the activation
-  // image and the biases
+  // one array: the A ring, the W ring, the activation image and the biases
   __shared__ __attribute__((aligned(16)))
   bf16raw smem[MP_NA * A_EL + MP_NW * B_EL + IMG_EL + SB_EL];
   bf16raw* const a_ring = smem;
@@ -169,12 +119,8 @@ __global__ __launch_bounds__(MP_THREADS, 2) void mlp_predict_kernel(const MlpPre
   // holds k = ks*32 + kg*8 .. +7) and the lane's bias
   const int H = p.n[L - 1];
   const bf16raw* const wh = p.w[L];
-  mp_frag_t wk[MP_BN / 32];
-#pragma unroll
-  for (int ks = 0; ks < MP_BN / 32; ++ks) {
-    wk[ks] = mp_frag_t{};
-    if (ks * 32 < H && l15 < C) wk[ks] = *(const mp_frag_t*)&wh[l15 * H + ks * 32 + kg * 8];
-  }
+  mt_frag_t wk[MP_BN / 32];
+  mt_head_w_frags(wk, wh, H, C, l15, kg);
   const bool head_bias = p.b[L] != nullptr;
   float bias_c = 0.f;
   if (head_bias && l15 < C) bias_c = p.b[L][l15];
@@ -184,20 +130,20 @@ __global__ __launch_bounds__(MP_THREADS, 2) void mlp_predict_kernel(const MlpPre
   auto stage_a = [&](int slot, int64_t m0, int kt) -> bool {
     bf16raw* an = a_ring + slot * A_EL;
     if (m0 + MP_BM <= M && kt + BKT <= K0) {
-      mp_dma_kmajor<MP_BM, BKT>(p.x, an, m0, MP_BM, K0, kt, wid, lane);
+      mt_dma_kmajor<MP_WAVES, MP_BM, BKT, true>(p.x, an, m0, MP_BM, K0, kt, wid, lane);
       return true;
     }
-    mp_fill_kmajor<MP_BM, BKT>(p.x, an, m0, M, K0, kt, K0, t);
+    mt_fill_kmajor<MP_THREADS, MP_BM, BKT>(p.x, an, m0, M, K0, kt, K0, t);
     return false;
   };
   // W[N][K] slab kt -> ring slot; true when it went by DMA (MP_W_DMA per wave)
   auto stage_b = [&](int slot, const bf16raw* W, int N, int K, int kt) -> bool {
     bf16raw* bn = b_ring + slot * B_EL;
     if (kt + BKT <= K) {
-      mp_dma_kmajor<MP_BN, BKT>(W, bn, 0, N, K, kt, wid, lane);
+      mt_dma_kmajor<MP_WAVES, MP_BN, BKT, true>(W, bn, 0, N, K, kt, wid, lane);
       return true;
     }
-    mp_fill_kmajor<MP_BN, BKT>(W, bn, 0, N, K, kt, K, t);
+    mt_fill_kmajor<MP_THREADS, MP_BN, BKT>(W, bn, 0, N, K, kt, K, t);
     return false;
   };
 
@@ -213,32 +159,28 @@ __global__ __launch_bounds__(MP_THREADS, 2) void mlp_predict_kernel(const MlpPre
   // staged slab (ab) or, for ab == nullptr, from columns kt.. of the image
   auto mma = [&](const bf16raw* ab, const bf16raw* bb, int kt, bool from_img, bool active) {
     if (!active) return;
-    mp_frag_t a[4], b[4];
+    mt_frag_t a[4], b[4];
 #pragma unroll
     for (int mi = 0; mi < 4; ++mi) {
       const int row = wr * 64 + mi * 16 + l15;
       if (from_img)
-        a[mi] = *(const mp_frag_t*)&img[row * MP_BN + ((((kt >> 3) + kg) ^ (row & IMG_XM)) << 3)];
+        a[mi] = mt_ld_frag<MP_BN, IMG_XM>(img, row, (kt >> 3) + kg);
       else
-        a[mi] = *(const mp_frag_t*)&ab[row * BKT + ((kg ^ (row & (SLOTS - 1))) << 3)];
+        a[mi] = mt_ld_frag<BKT, SLOTS - 1>(ab, row, kg);
     }
 #pragma unroll
     for (int ni = 0; ni < 4; ++ni) {
       const int rowb = wc * 64 + ni * 16 + l15;
-      b[ni] = *(const mp_frag_t*)&bb[rowb * BKT + ((kg ^ (rowb & (SLOTS - 1))) << 3)];
+      b[ni] = mt_ld_frag<BKT, SLOTS - 1>(bb, rowb, kg);
     }
-#pragma unroll
-    for (int mi = 0; mi < 4; ++mi)
-#pragma unroll
-      for (int ni = 0; ni < 4; ++ni)
-        acc[mi][ni] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[mi], b[ni], acc[mi][ni], 0, 0, 0);
+    mt_mma_tile(acc, a, b);
   };
 
-  // acc -> relu(acc + bias) as bf16 into the image (linear_stream's epilogue
-  // arithmetic).  Accumulator element r of lane (l15, kg) is row
-  // mi*16 + kg*4 + r, column ni*16 + l15 of the wave's sub-tile: 16 lanes
-  // write 32 contiguous bytes and the four lane groups land 64 B apart, so
-  // the 2-byte stores are conflict-free.
+  // acc -> relu(acc + bias) as bf16 into the image (mt_epi_slice's rounding
+  // order; the store differs, so it stays here).  Accumulator element r of
+  // lane (l15, kg) is row mi*16 + kg*4 + r, column ni*16 + l15 of the wave's
+  // sub-tile: 16 lanes write 32 contiguous bytes and the four lane groups
+  // land 64 B apart, so the 2-byte stores are conflict-free.
   auto epilogue = [&](int l, bool has_bias) {
     const float* bl = sbias + l * MP_BN;
 #pragma unroll
@@ -351,15 +293,7 @@ __global__ __launch_bounds__(MP_THREADS, 2) void mlp_predict_kernel(const MlpPre
     // ---- head: logits of rows wid*16 .. +15 from the image, argmax ----
     {
       const int arow = wid * 16 + l15;
-      floatx4 lg = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-      for (int ks = 0; ks < MP_BN / 32; ++ks) {
-        if (ks * 32 < H) {
-          const mp_frag_t ay =
-              *(const mp_frag_t*)&img[arow * MP_BN + (((ks * 4 + kg) ^ (arow & IMG_XM)) << 3)];
-          lg = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ay, wk[ks], lg, 0, 0, 0);
-        }
-      }
+      const floatx4 lg = mt_head_logits<MP_BN / 32, MP_BN, IMG_XM>(wk, img, arow, H, kg);
       // lane (class l15, kg), element r <-> tile row wid*16 + kg*4 + r
       int best[4];
 #pragma unroll

@@ -61,7 +61,7 @@ int main(int argc, char** argv) {
           } else {
             CKB(launch_linear_stream(a, w, c[v], s.dgrad ? nullptr : bias,
                                      s.dgrad ? mask : nullptr, M, s.N, s.K,
-                                     s.dgrad ? LS_EPI_MASK : LS_EPI_BIAS_RELU, s.dgrad,
+                                     s.dgrad ? EPI_BF16_MASK : EPI_BIAS_RELU, s.dgrad,
                                      v == 1 ? 32 : 64, 0));
           }
         }
