@@ -419,6 +419,45 @@ extern "C" hipError_t launch_small_wgrad(const bf16raw* dz, const bf16raw* col, 
 }
 
 // ---------------------------------------------------------------------------
+// NaN-keeping conversions of the cast kernels
+// ---------------------------------------------------------------------------
+
+// f32 -> bf16 for the cast kernels only: user data may carry NaNs with any
+// payload, and the rounding add of common.h's f32_to_bf16 carries a low-payload
+// NaN into Inf (0x7F800001) or across the sign into zero (0x7FFFFFFF).  A NaN
+// becomes a quiet NaN of the same sign here; everything else rounds as there.
+// The test is on the bits: the build's -ffast-math folds x != x away.
+// (Arithmetic NaNs are canonical 0x7FC00000 and survive f32_to_bf16, which
+// the hot kernels keep.)
+__device__ __forceinline__ bf16raw cast_f32_to_bf16(float f) {
+  union {
+    float f;
+    uint32_t u;
+  } c;
+  c.f = f;
+  if ((c.u & 0x7fffffffu) > 0x7f800000u) return (bf16raw)((c.u >> 16) | 0x0040u);
+  return f32_to_bf16(f);
+}
+
+// f64 -> f32 with NaN kept by a test on the bits, for the same reason.
+__device__ __forceinline__ float cast_f64_to_f32(double d) {
+  union {
+    double d;
+    uint64_t u;
+  } c;
+  c.d = d;
+  if ((c.u & 0x7fffffffffffffffull) > 0x7ff0000000000000ull) {
+    union {
+      uint32_t u;
+      float f;
+    } q;
+    q.u = ((uint32_t)(c.u >> 32) & 0x80000000u) | 0x7fc00000u;
+    return q.f;
+  }
+  return (float)d;
+}
+
+// ---------------------------------------------------------------------------
 // fp64 -> fp32 cast (Spark DenseVector pack)
 // ---------------------------------------------------------------------------
 
@@ -426,7 +465,7 @@ __global__ void cast_f64_f32_kernel(const double* __restrict__ src, float* __res
                                     int64_t n) {
   int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   int64_t stride = (int64_t)gridDim.x * blockDim.x;
-  for (int64_t k = i; k < n; k += stride) dst[k] = (float)src[k];
+  for (int64_t k = i; k < n; k += stride) dst[k] = cast_f64_to_f32(src[k]);
 }
 
 extern "C" hipError_t launch_cast_f64_f32(const double* src, float* dst, int64_t n,
@@ -451,10 +490,11 @@ __global__ void cast_f64_bf16_kernel(const double* __restrict__ src, bf16raw* __
   const doublex2* s2 = (const doublex2*)src;
   for (int64_t k = i; k < nvec; k += stride) {
     doublex2 v = s2[k];
-    dst[2 * k] = f32_to_bf16((float)v[0]);
-    dst[2 * k + 1] = f32_to_bf16((float)v[1]);
+    dst[2 * k] = cast_f32_to_bf16(cast_f64_to_f32(v[0]));
+    dst[2 * k + 1] = cast_f32_to_bf16(cast_f64_to_f32(v[1]));
   }
-  for (int64_t k = (nvec << 1) + i; k < n; k += stride) dst[k] = f32_to_bf16((float)src[k]);
+  for (int64_t k = (nvec << 1) + i; k < n; k += stride)
+    dst[k] = cast_f32_to_bf16(cast_f64_to_f32(src[k]));
 }
 
 extern "C" hipError_t launch_cast_f64_bf16(const double* src, bf16raw* dst, int64_t n,
@@ -480,10 +520,10 @@ __global__ void cast_f32_bf16_kernel(const float* __restrict__ src, bf16raw* __r
     floatx4 v = s4[k];
     shortx4 o;
 #pragma unroll
-    for (int j = 0; j < 4; ++j) o[j] = (short)f32_to_bf16(v[j]);
+    for (int j = 0; j < 4; ++j) o[j] = (short)cast_f32_to_bf16(v[j]);
     d4[k] = o;
   }
-  for (int64_t k = (nvec << 2) + i; k < n; k += stride) dst[k] = f32_to_bf16(src[k]);
+  for (int64_t k = (nvec << 2) + i; k < n; k += stride) dst[k] = cast_f32_to_bf16(src[k]);
 }
 
 extern "C" hipError_t launch_cast_f32_bf16(const float* src, bf16raw* dst, int64_t n,

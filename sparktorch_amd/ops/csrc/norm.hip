@@ -23,6 +23,13 @@
 // Pass 1: grid (C, S) blocks; block (c, s) reduces a slice of the B*HW
 // per-channel elements into LDS, then one atomicAdd per block into
 // sum[c] / sumsq[c] (fp32, caller-zeroed).
+//
+// All stats kernels (NCHW and NHWC) accumulate sums SHIFTED by a per-channel
+// pivot p = the channel's first element, which every block can read:
+// s = sum(x - p), ss = sum((x - p)^2); the finalize re-reads p and finishes
+// mean = p + s/n, var = ss/n - (s/n)^2.  Unshifted one-pass E[x^2] - E[x]^2
+// loses log2((mean/std)^2) bits in fp32: at mean/std = 32 invstd was already
+// 1e-4 off, at 200 it was 0.4 % off (profiles/bn_stats_shift.md).
 // ---------------------------------------------------------------------------
 
 __global__ void bn_stats_partial_kernel(const bf16raw* __restrict__ x, float* __restrict__ sum,
@@ -32,11 +39,12 @@ __global__ void bn_stats_partial_kernel(const bf16raw* __restrict__ x, float* __
   int64_t per = ceil_div_i64(total, gridDim.y);
   int64_t lo = (int64_t)blockIdx.y * per;
   int64_t hi = lo + per < total ? lo + per : total;
+  const float pivot = bf16_to_f32(x[(int64_t)c * HW]);
   float s = 0.f, ss = 0.f;
   for (int64_t i = lo + threadIdx.x; i < hi; i += blockDim.x) {
     int64_t b = i / HW;
     int64_t hw = i - b * HW;
-    float v = bf16_to_f32(x[(b * C + c) * HW + hw]);
+    float v = bf16_to_f32(x[(b * C + c) * HW + hw]) - pivot;
     s += v;
     ss += v * v;
   }
@@ -58,16 +66,19 @@ __global__ void bn_stats_partial_kernel(const bf16raw* __restrict__ x, float* __
 }
 
 // Pass 2: mean/invstd for normalization (biased var) + running-stat update
-// (unbiased var, torch semantics).  One tiny launch over C.
-__global__ void bn_stats_finalize_kernel(const float* __restrict__ sum,
+// (unbiased var, torch semantics).  One tiny launch over C.  The pivot of
+// channel c is x[c * pivot_stride] (HW for NCHW, 1 for NHWC).
+__global__ void bn_stats_finalize_kernel(const bf16raw* __restrict__ x, int64_t pivot_stride,
+                                         const float* __restrict__ sum,
                                          const float* __restrict__ sumsq,
                                          float* __restrict__ mean, float* __restrict__ invstd,
                                          float* __restrict__ running_mean,
                                          float* __restrict__ running_var, int64_t count,
                                          float momentum, float eps, int C) {
   for (int c = blockIdx.x * blockDim.x + threadIdx.x; c < C; c += gridDim.x * blockDim.x) {
-    float mu = sum[c] / (float)count;
-    float var = sumsq[c] / (float)count - mu * mu;
+    float d = sum[c] / (float)count;
+    float mu = bf16_to_f32(x[(int64_t)c * pivot_stride]) + d;
+    float var = sumsq[c] / (float)count - d * d;
     var = var > 0.f ? var : 0.f;
     mean[c] = mu;
     invstd[c] = rsqrtf(var + eps);
@@ -87,9 +98,9 @@ extern "C" hipError_t launch_bn_stats(const bf16raw* x, float* sum, float* sumsq
   bn_stats_partial_kernel<<<grid, 256, 0, stream>>>(x, sum, sumsq, B, C, HW);
   HIP_CHECK_LAUNCH();
   int blocks = (int)ceil_div_i64(C, 256);
-  bn_stats_finalize_kernel<<<blocks, 256, 0, stream>>>(sum, sumsq, mean, invstd, running_mean,
-                                                       running_var, (int64_t)B * HW, momentum,
-                                                       eps, C);
+  bn_stats_finalize_kernel<<<blocks, 256, 0, stream>>>(x, HW, sum, sumsq, mean, invstd,
+                                                       running_mean, running_var,
+                                                       (int64_t)B * HW, momentum, eps, C);
   HIP_CHECK_LAUNCH();
   return hipSuccess;
 }
@@ -111,8 +122,9 @@ __global__ void bn_stats_partial_nhwc_kernel(const bf16raw* __restrict__ x,
   int64_t hi = lo + per < M ? lo + per : M;
   float s = 0.f, ss = 0.f;
   if (c < C) {
+    const float pivot = bf16_to_f32(x[c]);
     for (int64_t r = lo + row_g; r < hi; r += 4) {
-      float v = bf16_to_f32(x[r * C + c]);
+      float v = bf16_to_f32(x[r * C + c]) - pivot;
       s += v;
       ss += v * v;
     }
@@ -147,11 +159,15 @@ __global__ void bn_stats_partial_nhwc_vec_kernel(const bf16raw* __restrict__ x,
   int64_t lo = (int64_t)blockIdx.x * per;
   int64_t hi = lo + per < M ? lo + per : M;
   float s[8] = {0, 0, 0, 0, 0, 0, 0, 0}, ss[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+  const shortx8 p8 = *(const shortx8*)(x + c0);  // row 0: the channels' pivots
+  float pivot[8];
+#pragma unroll
+  for (int j = 0; j < 8; ++j) pivot[j] = bf16_to_f32((bf16raw)p8[j]);
   for (int64_t r = lo + rg; r < hi; r += rpg) {
     const shortx8 v = *(const shortx8*)(x + r * C + c0);
 #pragma unroll
     for (int j = 0; j < 8; ++j) {
-      float f = bf16_to_f32((bf16raw)v[j]);
+      float f = bf16_to_f32((bf16raw)v[j]) - pivot[j];
       s[j] += f;
       ss[j] += f * f;
     }
@@ -179,7 +195,8 @@ __global__ void bn_stats_partial_nhwc_vec_kernel(const bf16raw* __restrict__ x,
 
 // reduce [S, C] partials and finish mean/invstd + running update.
 // One block per channel: 256 threads stride the S partial rows, LDS tree.
-__global__ void bn_stats_finalize2_kernel(const float* __restrict__ psum,
+__global__ void bn_stats_finalize2_kernel(const bf16raw* __restrict__ x,
+                                          const float* __restrict__ psum,
                                           const float* __restrict__ psumsq, int S,
                                           float* __restrict__ mean, float* __restrict__ invstd,
                                           float* __restrict__ running_mean,
@@ -205,8 +222,9 @@ __global__ void bn_stats_finalize2_kernel(const float* __restrict__ psum,
     }
     if (threadIdx.x != 0) return;
     float sum = l0[0], sumsq = l1[0];
-    float mu = sum / (float)count;
-    float var = sumsq / (float)count - mu * mu;
+    float d = sum / (float)count;
+    float mu = bf16_to_f32(x[c]) + d;  // x[c]: the pivot the partials were shifted by
+    float var = sumsq / (float)count - d * d;
     var = var > 0.f ? var : 0.f;
     mean[c] = mu;
     invstd[c] = rsqrtf(var + eps);
@@ -229,7 +247,7 @@ extern "C" hipError_t launch_bn_stats_nhwc(const bf16raw* x, float* sum, float* 
     bn_stats_partial_nhwc_vec_kernel<<<S, 256, 0, stream>>>(x, scratch, scratch + (int64_t)S * C,
                                                             M, C);
     HIP_CHECK_LAUNCH();
-    bn_stats_finalize2_kernel<<<C, 256, 0, stream>>>(scratch, scratch + (int64_t)S * C, S,
+    bn_stats_finalize2_kernel<<<C, 256, 0, stream>>>(x, scratch, scratch + (int64_t)S * C, S,
                                                      mean, invstd, running_mean, running_var, M,
                                                      momentum, eps, C);
     HIP_CHECK_LAUNCH();
@@ -239,8 +257,9 @@ extern "C" hipError_t launch_bn_stats_nhwc(const bf16raw* x, float* sum, float* 
   bn_stats_partial_nhwc_kernel<<<grid, 256, 0, stream>>>(x, sum, sumsq, M, C);
   HIP_CHECK_LAUNCH();
   int blocks = (int)ceil_div_i64(C, 256);
-  bn_stats_finalize_kernel<<<blocks, 256, 0, stream>>>(sum, sumsq, mean, invstd, running_mean,
-                                                       running_var, M, momentum, eps, C);
+  bn_stats_finalize_kernel<<<blocks, 256, 0, stream>>>(x, 1, sum, sumsq, mean, invstd,
+                                                       running_mean, running_var, M, momentum,
+                                                       eps, C);
   HIP_CHECK_LAUNCH();
   return hipSuccess;
 }

@@ -164,16 +164,48 @@ class FusedSGD(_FusedOptimizerBase):
                 p.add_(g, alpha=-self.lr)
 
 
+def _same_settings(a: dict, b: dict) -> bool:
+    if a.keys() != b.keys():
+        return False
+    for k, va in a.items():
+        vb = b[k]
+        if isinstance(va, torch.Tensor) or isinstance(vb, torch.Tensor):
+            if not (isinstance(va, torch.Tensor) and isinstance(vb, torch.Tensor)
+                    and va.shape == vb.shape and torch.equal(va, vb)):
+                return False
+        elif va != vb:
+            return False
+    return True
+
+
 def fused_optimizer_for(torch_opt: torch.optim.Optimizer, buckets: FlatBuckets):
     """Map a hydrated torch optimizer onto its fused flat-bucket equivalent.
 
     Returns None when no fused mapping exists (trainer then keeps the torch
-    optimizer, re-bound to the flattened params).
+    optimizer, re-bound to the flattened params): another optimizer class,
+    ``amsgrad=True``, ``maximize=True``, or several param groups whose
+    hyper-parameters differ.  The hyper-parameters are read from the live
+    param group, so edits made after construction count.
     """
     # NB: match by class NAME, not isinstance — dill round-trips torch classes
     # by value, so a deserialized Adam is a distinct class object.
-    d = torch_opt.defaults
     name = type(torch_opt).__name__
+    if name not in ("AdamW", "Adam", "SGD"):
+        return None
+    # The fused optimizers run ONE set of hyper-parameters over every bucket
+    # and know neither amsgrad nor maximize: anything else keeps torch's maths
+    # by keeping torch's optimizer.
+    groups = torch_opt.param_groups
+    if not groups:
+        return None
+    settings = [{k: v for k, v in g.items() if k != "params"} for g in groups]
+    if any(not _same_settings(s, settings[0]) for s in settings[1:]):
+        return None
+    # the live group, not the constructor defaults: an lr (or anything else)
+    # edited in param_groups after construction is what torch would step with
+    d = settings[0]
+    if d.get("amsgrad", False) or d.get("maximize", False):
+        return None
     if name == "AdamW":
         return FusedAdam(
             buckets,

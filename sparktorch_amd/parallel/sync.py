@@ -118,9 +118,22 @@ class SyncTrainer:
         if self.optimizer is None:
             # No fused mapping: rebuild the torch optimizer on the re-bound
             # (flattened) parameters; averaging happens in finalize().
-            self._torch_opt = type(torch_optimizer)(
-                self.model.parameters(), **torch_optimizer.defaults
-            )
+            # Param groups (and settings edited in them after construction)
+            # carry over when the model still holds the optimizer's very
+            # parameters; a conversion that replaced them leaves only the
+            # constructor defaults to go by.
+            live = {id(p) for p in self.model.parameters()}
+            groups = torch_optimizer.param_groups
+            if groups and all(id(p) in live for g in groups for p in g["params"]) and sum(
+                len(g["params"]) for g in groups
+            ) == len(live):
+                self._torch_opt = type(torch_optimizer)(
+                    [dict(g) for g in groups], **torch_optimizer.defaults
+                )
+            else:
+                self._torch_opt = type(torch_optimizer)(
+                    self.model.parameters(), **torch_optimizer.defaults
+                )
 
         self._graph = None
         self._graph_inputs = None

@@ -67,11 +67,13 @@ def test_bn_eval_uses_running_stats():
     beta = torch.randn(C, device=DEV)
     rm = torch.randn(C, device=DEV) * 0.3
     rv = torch.rand(C, device=DEV) + 0.5
+    rm0, rv0 = rm.clone(), rv.clone()
     y = hip_batch_norm2d(bf(x), gamma, beta, rm, rv, training=False)
-    y2 = F.batch_norm(bf(x).float(), rm.clone(), rv.clone(), gamma, beta, False, 0.1, 1e-5)
+    y2 = F.batch_norm(bf(x).float(), rm0.clone(), rv0.clone(), gamma, beta, False, 0.1, 1e-5)
     assert torch.allclose(y.float(), y2, atol=2e-2, rtol=2e-2)
     # eval must not touch running stats
-    assert torch.allclose(rv, rv)
+    assert torch.equal(rm, rm0)
+    assert torch.equal(rv, rv0)
 
 
 def test_bn_fused_relu_matches_separate():
