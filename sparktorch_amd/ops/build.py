@@ -20,8 +20,13 @@ OPS_DIR = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(OPS_DIR, "csrc")
 BUILD_DIR = os.path.join(OPS_DIR, "build")
 
-HIP_SOURCES = ["elementwise.hip", "loss.hip", "gemm.hip", "conv.hip", "norm.hip", "conv_nhwc.hip", "conv_implicit.hip", "head_bwd.hip", "linear_wgrad.hip", "sample_gather.hip", "linear_stream.hip", "mlp_predict.hip"]
+HIP_SOURCES = ["elementwise.hip", "loss.hip", "gemm.hip", "conv.hip", "norm.hip", "conv_nhwc.hip", "conv_implicit.hip", "head_bwd.hip", "linear_wgrad.hip", "sample_gather.hip", "linear_stream.hip", "mlp_predict.hip", "hidden_bwd.hip"]
 CPP_SOURCES = ["bindings.cpp"]
+# Extra hipcc flags per translation unit.  hidden_bwd.hip is compiled without
+# packed fp32 instructions (v_pk_*_f32).
+HIP_EXTRA_FLAGS = {
+    "hidden_bwd.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"],
+}
 
 ROCM = os.environ.get("ROCM_PATH", "/opt/rocm")
 ARCH = os.environ.get("PYTORCH_ROCM_ARCH", "gfx950")
@@ -95,6 +100,9 @@ def build_extension(
                 "-std=c++17",
                 "-fPIC",
                 "-ffast-math",
+            ]
+            + HIP_EXTRA_FLAGS.get(s, [])
+            + [
                 "-c",
                 os.path.join(CSRC, s),
                 "-o",

@@ -50,6 +50,10 @@ int linear_wgrad_stream_supported(int, int, int64_t);
 int linear_wgrad_stream_can_run(int, int, int64_t);
 hipError_t launch_linear_wgrad_stream(const bf16raw*, const bf16raw*, float*, float*, int64_t, int,
                                       int, int, int, hipStream_t);
+int hidden_bwd_supported(int, int, int64_t);
+int hidden_bwd_can_run(int, int, int64_t);
+hipError_t launch_hidden_bwd(const bf16raw*, const bf16raw*, const bf16raw*, bf16raw*, float*,
+                             float*, int64_t, int, int, int, int, hipStream_t);
 int linear_fwd_stream_supported(int, int, int64_t);
 int64_t linear_fwd_stream_min_rows();
 hipError_t launch_linear_stream(const bf16raw*, const bf16raw*, bf16raw*, const float*,
@@ -797,6 +801,58 @@ void linear_wgrad_stream(at::Tensor dz, at::Tensor x, at::Tensor dw, c10::option
                                        (int)max_blocks, head_num_cus(), cur_stream()));
 }
 
+// One-pass backward of a hidden Linear on a ReLU output (hidden_bwd.hip):
+// returns dz_in = (dz @ w) * (x_in > 0), bit-identical to linear_dgrad_relu,
+// and accumulates dw / db under linear_wgrad_stream's contract.
+// linear_hidden_bwd_ok is the routing rule (shape set and measured batch
+// threshold); the launcher serves every batch linear_hidden_bwd_runs accepts.
+bool linear_hidden_bwd_runs(int64_t No, int64_t Ki, int64_t B) {
+  return No <= 256 && Ki < (1 << 24) && hidden_bwd_can_run((int)No, (int)Ki, B) != 0;
+}
+bool linear_hidden_bwd_ok(int64_t No, int64_t Ki, int64_t B) {
+  return No <= 256 && Ki < (1 << 24) && hidden_bwd_supported((int)No, (int)Ki, B) != 0;
+}
+
+at::Tensor linear_hidden_bwd(at::Tensor dz, at::Tensor w, at::Tensor x_in, at::Tensor dw,
+                             c10::optional<at::Tensor> db, int64_t max_blocks,
+                             c10::optional<at::Tensor> out) {
+  check_gpu_contig(dz, at::kBFloat16, "dz");
+  check_gpu_contig(w, at::kBFloat16, "w");
+  check_gpu_contig(x_in, at::kBFloat16, "x_in");
+  check_gpu_contig(dw, at::kFloat, "dw");
+  TORCH_CHECK(dz.dim() == 2 && x_in.dim() == 2 && w.dim() == 2);
+  int64_t B = dz.size(0), N = dz.size(1), K = x_in.size(1);
+  TORCH_CHECK(x_in.size(0) == B && w.size(0) == N && w.size(1) == K && dw.size(0) == N &&
+                  dw.size(1) == K,
+              "shape mismatch");
+  float* dbp = nullptr;
+  if (db.has_value()) {
+    check_gpu_contig(*db, at::kFloat, "db");
+    TORCH_CHECK(db->numel() == N);
+    dbp = db->data_ptr<float>();
+  }
+  TORCH_CHECK(linear_hidden_bwd_runs(N, K, B),
+              "linear_hidden_bwd: unsupported (No, Ki, B); use linear_dgrad_relu and "
+              "linear_wgrad_into");
+  TORCH_CHECK(aligned16(dz) && aligned16(x_in),
+              "linear_hidden_bwd wants 16-byte aligned dz and x_in");
+  // out: tests place dz_in inside a guarded buffer
+  at::Tensor dz_in;
+  if (out.has_value()) {
+    dz_in = *out;
+    check_gpu_contig(dz_in, at::kBFloat16, "out");
+    TORCH_CHECK(dz_in.dim() == 2 && dz_in.size(0) == B && dz_in.size(1) == K && aligned16(dz_in),
+                "out must be a 16-byte aligned [B, Ki]");
+  } else {
+    dz_in = at::empty({B, K}, dz.options());
+  }
+  CHECK_HIP(launch_hidden_bwd((const bf16raw*)dz.data_ptr(), (const bf16raw*)x_in.data_ptr(),
+                              (const bf16raw*)w.data_ptr(), (bf16raw*)dz_in.data_ptr(),
+                              dw.data_ptr<float>(), dbp, B, (int)N, (int)K, (int)max_blocks,
+                              head_num_cus(), cur_stream()));
+  return dz_in;
+}
+
 void bias_grad_into(at::Tensor dz, at::Tensor db) {
   check_gpu_contig(dz, at::kBFloat16, "dz");
   check_gpu_contig(db, at::kFloat, "db");
@@ -1332,6 +1388,14 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("linear_wgrad_stream", &linear_wgrad_stream,
         "dW (+ db) accumulated by the persistent batch-streaming kernel", py::arg("dz"),
         py::arg("x"), py::arg("dw"), py::arg("db") = py::none(), py::arg("max_blocks") = 0);
+  m.def("linear_hidden_bwd_supported", &linear_hidden_bwd_ok,
+        "is (No, Ki) at batch B routed to the one-pass hidden-layer backward");
+  m.def("linear_hidden_bwd_can_run", &linear_hidden_bwd_runs,
+        "can the one-pass hidden-layer backward compute (No, Ki, B) at all");
+  m.def("linear_hidden_bwd", &linear_hidden_bwd,
+        "masked dz_in returned, dW (+ db) accumulated, one pass over dz and x_in", py::arg("dz"),
+        py::arg("w"), py::arg("x_in"), py::arg("dw"), py::arg("db") = py::none(),
+        py::arg("max_blocks") = 0, py::arg("out") = py::none());
   m.def("linear_wgrad", &linear_wgrad, "dW = dZ^T X, MFMA split-K");
   m.def("linear_wgrad_into", &linear_wgrad_into, "dW accumulated into grad view");
   m.def("linear_wgrad_bias_into", &linear_wgrad_bias_into, "dW + db in one MFMA launch");

@@ -31,30 +31,14 @@
 // the last column tile are clamped to the row's last 16 B slot and are never
 // flushed (MFMA output columns are independent).
 
-#include "mfma_tile.h"
+//
+// A hidden layer on a ReLU output whose input gradient is wanted as well gets
+// dW, db and the masked dgrad from one pass over the same two tensors:
+// hidden_bwd.hip, which shares this file's tile image (linear_wgrad_tile.h).
+
+#include "linear_wgrad_tile.h"
 
 #define LWG_THREADS 256
-#define LWG_ROWS 32    // batch rows per tile = one 16x16x32 k-step
-#define LWG_SPLIT_TILES 64  // register chains this long (2048 rows) are flushed half-way
-#define LWG_XCOLS 128  // x image row: 16 slots of 16 B (NF = 7 leaves two unused)
-
-// Slot swizzle.  A transposing read's 32-lane half covers an aligned group of
-// 8 rows x 32 B (one 16-column fragment = an aligned slot pair per row); the
-// key moves the 8 rows' pairs onto 8 distinct 32 B bank groups.
-template <int SLOTS>
-struct lwg_key {
-  static __device__ __forceinline__ int key(int row) {
-    return SLOTS >= 16 ? ((row & 7) << 1) : (((row >> 1) & 3) << 1);
-  }
-};
-
-// fragment value i <-> tile row (i/4)*16 + q*4 + (i%4), column col0 + l15
-// (the same row order for both operands, so the k pairing is consistent)
-template <int SLOTS>
-__device__ __forceinline__ mt_frag_t lwg_tr_frag(const bf16raw* __restrict__ img, int q, int l15,
-                                                 int col0) {
-  return mt_tr_frag<SLOTS * 8, 4, 16, lwg_key<SLOTS>>(img, 0, q, l15, col0);
-}
 
 // MF: 16-row dW fragments per wave (No = 64 * MF); NF: 16-column fragments
 // of the x tile (tile width 16 * NF)
@@ -238,18 +222,10 @@ __global__ __launch_bounds__(LWG_THREADS, 2) void linear_wgrad_kernel(
   }
 }
 
-// x tile width in 16-column fragments: the one of {7, 8} that covers Ki with
-// fewer dead columns (784 = 7 x 112; 256 = 2 x 128)
-static int lwg_nf(int Ki) {
-  const int c7 = (Ki + 111) / 112 * 112, c8 = (Ki + 127) / 128 * 128;
-  return c7 < c8 ? 7 : 8;
-}
-
 // Smallest batch at which the kernel was measured against the split-K route
 // of gemm.hip (and won at both flagship shapes); below it that route stays
 // (profiles/bench_resnet18_optimization_log.md, "Streaming wgrad").
 #define LWG_MIN_BATCH 32768
-#define LWG_MIN_TILES 16
 
 // 1 when the kernel can compute (No, Ki, B) at all
 extern "C" int linear_wgrad_stream_can_run(int No, int Ki, int64_t B) {

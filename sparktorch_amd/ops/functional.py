@@ -9,7 +9,9 @@ backward:
                                  batches: persistent streaming kernel with db
   db = colsum(dz)              — bias_grad
 Layer stacks (hip_mlp_chain) fold the ReLU mask into the consumer's dgrad
-epilogue and run a small classifier head's whole backward in one pass; a
+epilogue, give a big-batch hidden layer on a ReLU output its masked dgrad, dW
+and db from one pass over dz and its input (hidden_bwd.hip), and run a small
+classifier head's whole backward in one pass; a
 train step under cross-entropy (mlp_chain_ce_step) also folds the head's
 forward and the loss into that pass.
 
@@ -114,6 +116,46 @@ def _linear_param_grads(ext, dz, x, w, b, need_w: bool, need_b: bool):
 # Tests flip this to pin Linear forward / dgrad to gemm.hip's tiles; on, the
 # bindings route big-batch N in (128, 256] shapes to linear_stream.hip.
 _LINEAR_STREAM = True
+
+
+# Tests flip this to keep a hidden layer's backward on its two launches
+# (linear_dgrad_relu, then the wgrad).
+_HIDDEN_BWD_FUSION = True
+
+
+def _hidden_bwd_ok(ext, dz: torch.Tensor, xin: torch.Tensor, wb: torch.Tensor) -> bool:
+    """Does the one-pass kernel (hidden_bwd.hip) replace linear_dgrad_relu +
+    linear_wgrad_into for this layer: both streaming routes on, the wgrad's
+    alignment and batch rule met, and a shape and batch the kernel is routed
+    (with the batch override: can run)."""
+    if not (_HIDDEN_BWD_FUSION and _LINEAR_STREAM and wb.dtype == torch.bfloat16
+            and wb.is_contiguous() and _wgrad_stream_ok(ext, dz, xin)):
+        return False
+    B, n_out, k_in = dz.shape[0], dz.shape[1], xin.shape[1]
+    if _WGRAD_STREAM_MIN_BATCH is None:
+        return ext.linear_hidden_bwd_supported(n_out, k_in, B)
+    return ext.linear_hidden_bwd_can_run(n_out, k_in, B)
+
+
+def _hidden_bwd(ext, dz, xin, w, wb, b, need_b):
+    """One-pass hidden-layer backward with _linear_param_grads' gradient
+    rules: direct into the bucket views (+ notify, weight first) where
+    installed, else fresh zeroed tensors handed to autograd.  Returns
+    (dz_in, dw, db)."""
+    w_notify = getattr(w, "_bucket_notify", None)
+    b_notify = getattr(b, "_bucket_notify", None) if b is not None else None
+    w_direct = w_notify is not None and w.grad is not None
+    b_direct = need_b and b_notify is not None and b.grad is not None
+    dw_t = w.grad if w_direct else torch.zeros_like(w, dtype=torch.float32)
+    db_t = None
+    if need_b:
+        db_t = b.grad if b_direct else torch.zeros_like(b, dtype=torch.float32)
+    dz_prev = ext.linear_hidden_bwd(dz, wb, xin, dw_t, db_t, 0)
+    if w_direct:
+        w_notify()
+    if b_direct:
+        b_notify()
+    return dz_prev, (None if w_direct else dw_t), (None if b_direct else db_t)
 
 
 class _LinearFn(torch.autograd.Function):
@@ -248,6 +290,9 @@ class _MLPChainFn(torch.autograd.Function):
             if i == n - 1 and masked and not relus[i] and need_w and _head_bwd_ok(ext, wb):
                 dz, grads[2 * i], grads[2 * i + 1] = _MLPChainFn._head(ext, dz, xin, w, wb, b,
                                                                       need_b)
+                continue
+            if masked and need_w and _hidden_bwd_ok(ext, dz, xin, wb):
+                dz, grads[2 * i], grads[2 * i + 1] = _hidden_bwd(ext, dz, xin, w, wb, b, need_b)
                 continue
             dz_prev = None
             if masked:
@@ -443,6 +488,9 @@ def mlp_chain_ce_step(x: torch.Tensor, layers, target: torch.Tensor) -> torch.Te
         b._bucket_notify()
     for i in range(n - 2, -1, -1):
         w, b, _ = layers[i]
+        if i > 0 and layers[i - 1][2] and _hidden_bwd_ok(ext, dz, acts[i], wbs[i]):
+            dz, _, _ = _hidden_bwd(ext, dz, acts[i], w, wbs[i], b, b is not None)
+            continue
         dz_prev = None
         if i > 0 and layers[i - 1][2]:
             dz_prev = ext.linear_dgrad_relu(dz, wbs[i], acts[i], _LINEAR_STREAM)
