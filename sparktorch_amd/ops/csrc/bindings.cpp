@@ -56,8 +56,11 @@ hipError_t launch_hidden_bwd(const bf16raw*, const bf16raw*, const bf16raw*, bf1
                              float*, int64_t, int, int, int, int, hipStream_t);
 int linear_fwd_stream_supported(int, int, int64_t);
 int64_t linear_fwd_stream_min_rows();
+int linear_fwd_stream_deep_supported(int, int, int64_t);
+int64_t linear_fwd_stream_deep_min_rows();
 hipError_t launch_linear_stream(const bf16raw*, const bf16raw*, bf16raw*, const float*,
-                                const bf16raw*, int64_t, int, int, int, int, int, hipStream_t);
+                                const bf16raw*, int64_t, int, int, int, int, int, int,
+                                hipStream_t);
 hipError_t launch_sample_gather(const void*, int, const void*, int, void*, void*, int*, const int*,
                                 uint32_t, int64_t, int, int, int, int, hipStream_t);
 hipError_t launch_head_bwd(const bf16raw*, const bf16raw*, const bf16raw*, bf16raw*, float*,
@@ -359,6 +362,27 @@ int64_t set_linear_stream_min_rows(int64_t rows) {
   return old;
 }
 
+// The same for the row threshold between linear_stream.hip's two forwards.
+static int64_t g_stream_deep_min_rows = -1;
+
+int64_t linear_stream_deep_min_rows() {
+  return g_stream_deep_min_rows >= 0 ? g_stream_deep_min_rows : linear_fwd_stream_deep_min_rows();
+}
+
+int64_t set_linear_stream_deep_min_rows(int64_t rows) {
+  const int64_t old = g_stream_deep_min_rows;
+  g_stream_deep_min_rows = rows;
+  return old;
+}
+
+// launch_linear_stream's fwd_path for a routed forward: 2 = the deep-K
+// kernel, 1 = the 128-row kernel
+static int stream_fwd_path(int64_t N, int64_t K, int64_t M) {
+  return M >= linear_stream_deep_min_rows() && linear_fwd_stream_deep_supported((int)N, (int)K, M)
+             ? 2
+             : 1;
+}
+
 static bool stream_route(const at::Tensor& a, const at::Tensor& w, int64_t n_out, int64_t k_red,
                          int64_t M) {
   return w.scalar_type() == at::kBFloat16 && M >= linear_stream_min_rows() &&
@@ -390,7 +414,7 @@ at::Tensor linear_fwd(at::Tensor x, at::Tensor w, c10::optional<at::Tensor> bias
   if (allow_stream && stream_route(x, w, N, K, M)) {
     CHECK_HIP(launch_linear_stream((const bf16raw*)x.data_ptr(), (const bf16raw*)w.data_ptr(),
                                    (bf16raw*)y.data_ptr(), bptr, nullptr, M, (int)N, (int)K, epi,
-                                   /*b_kn*/ 0, 0, cur_stream()));
+                                   /*b_kn*/ 0, 0, stream_fwd_path(N, K, M), cur_stream()));
     return y;
   }
   CHECK_HIP(launch_gemm_bf16(x.data_ptr(), w.data_ptr(), w.scalar_type() == at::kFloat ? 1 : 0,
@@ -399,21 +423,28 @@ at::Tensor linear_fwd(at::Tensor x, at::Tensor w, c10::optional<at::Tensor> bias
   return y;
 }
 
-// The streaming kernel at any M (tests, microbenchmarks); bf16 w only.
+// The streaming kernels at any M (tests, microbenchmarks); bf16 w only.
+// path: 0 = what linear_fwd would pick at this shape from its row threshold
+// on, 1 = the 128-row kernel, 2 = the deep-K kernel (an error where it does
+// not serve the shape).
 at::Tensor linear_fwd_stream(at::Tensor x, at::Tensor w, c10::optional<at::Tensor> bias,
-                             bool relu) {
+                             bool relu, int64_t path) {
   check_gpu_contig(x, at::kBFloat16, "x");
   check_gpu_contig(w, at::kBFloat16, "w");
   TORCH_CHECK(x.dim() == 2 && w.dim() == 2 && w.size(1) == x.size(1), "shape mismatch");
   int64_t M = x.size(0), K = x.size(1), N = w.size(0);
   TORCH_CHECK(linear_fwd_stream_ok(N, K, M), "linear_fwd_stream: unsupported (N, K, M)");
   TORCH_CHECK(aligned16(x) && aligned16(w), "linear_fwd_stream wants 16-byte aligned x and w");
+  TORCH_CHECK(path >= 0 && path <= 2, "linear_fwd_stream: path is 0 (automatic), 1 or 2");
+  TORCH_CHECK(path != 2 || linear_fwd_stream_deep_supported((int)N, (int)K, M) != 0,
+              "linear_fwd_stream: the deep-K kernel wants K > 256");
+  if (path == 0) path = stream_fwd_path(N, K, M);
   auto y = at::empty({M, N}, x.options());
   const float* bptr = nullptr;
   const int epi = fwd_epi(bias, relu, &bptr);
   CHECK_HIP(launch_linear_stream((const bf16raw*)x.data_ptr(), (const bf16raw*)w.data_ptr(),
                                  (bf16raw*)y.data_ptr(), bptr, nullptr, M, (int)N, (int)K, epi, 0,
-                                 0, cur_stream()));
+                                 0, (int)path, cur_stream()));
   return y;
 }
 
@@ -426,7 +457,7 @@ at::Tensor linear_dgrad(at::Tensor dz, at::Tensor w, bool allow_stream) {
   if (allow_stream && stream_route(dz, w, K, N, M)) {
     CHECK_HIP(launch_linear_stream((const bf16raw*)dz.data_ptr(), (const bf16raw*)w.data_ptr(),
                                    (bf16raw*)dx.data_ptr(), nullptr, nullptr, M, (int)K, (int)N,
-                                   /*EPI_BF16*/ 1, /*b_kn*/ 1, 0, cur_stream()));
+                                   /*EPI_BF16*/ 1, /*b_kn*/ 1, 0, 0, cur_stream()));
     return dx;
   }
   CHECK_HIP(launch_gemm_bf16(dz.data_ptr(), w.data_ptr(), w.scalar_type() == at::kFloat ? 1 : 0,
@@ -451,7 +482,7 @@ at::Tensor linear_dgrad_relu(at::Tensor dz, at::Tensor w, at::Tensor y_prev, boo
     CHECK_HIP(launch_linear_stream((const bf16raw*)dz.data_ptr(), (const bf16raw*)w.data_ptr(),
                                    (bf16raw*)dx.data_ptr(), nullptr,
                                    (const bf16raw*)y_prev.data_ptr(), M, (int)K, (int)N,
-                                   /*EPI_BF16_MASK*/ 6, /*b_kn*/ 1, 0, cur_stream()));
+                                   /*EPI_BF16_MASK*/ 6, /*b_kn*/ 1, 0, 0, cur_stream()));
     return dx;
   }
   CHECK_HIP(launch_gemm_bf16_mask(dz.data_ptr(), w.data_ptr(),
@@ -481,7 +512,7 @@ at::Tensor linear_dgrad_stream(at::Tensor dz, at::Tensor w, c10::optional<at::Te
   auto dx = at::empty({M, K}, dz.options());
   CHECK_HIP(launch_linear_stream((const bf16raw*)dz.data_ptr(), (const bf16raw*)w.data_ptr(),
                                  (bf16raw*)dx.data_ptr(), nullptr, mptr, M, (int)K, (int)N,
-                                 mptr ? 6 : 1, /*b_kn*/ 1, 0, cur_stream()));
+                                 mptr ? 6 : 1, /*b_kn*/ 1, 0, 0, cur_stream()));
   return dx;
 }
 
@@ -1359,7 +1390,19 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("rows"));
   m.def("linear_fwd_stream", &linear_fwd_stream,
         "Y = X W^T (+bias)(+relu) through the full-N streaming kernel, any M", py::arg("x"),
-        py::arg("w"), py::arg("bias"), py::arg("relu"));
+        py::arg("w"), py::arg("bias"), py::arg("relu"), py::arg("path") = 0);
+  m.def("linear_fwd_stream_deep_supported",
+        [](int64_t N, int64_t K, int64_t M) {
+          return N <= 256 && K < (1 << 24) &&
+                 linear_fwd_stream_deep_supported((int)N, (int)K, M) != 0;
+        },
+        "does the deep-K forward of the streaming kernels (path 2) serve the shape",
+        py::arg("N"), py::arg("K"), py::arg("M"));
+  m.def("linear_fwd_stream_deep_min_rows", &linear_stream_deep_min_rows,
+        "M from which a routed K > 256 forward takes the deep-K kernel");
+  m.def("set_linear_stream_deep_min_rows", &set_linear_stream_deep_min_rows,
+        "override that M (tests); negative restores the measured one; returns the old setting",
+        py::arg("rows"));
   m.def("linear_dgrad_stream", &linear_dgrad_stream,
         "dX = dZ W (* (y_prev > 0)) through the full-N streaming kernel, any M", py::arg("dz"),
         py::arg("w"), py::arg("y_prev") = py::none());

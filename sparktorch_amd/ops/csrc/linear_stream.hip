@@ -250,6 +250,199 @@ __global__ __launch_bounds__(LS_THREADS, BKT == 32 ? 4 : 2) void linear_stream_k
   }
 }
 
+// ---- deep-K forward: K > 256, where W does not fit a CU ----
+//
+// At K = 784 the kernel above re-stages all of W once per 128 rows and each
+// wave runs DMA issue, fragment reads, wait, MFMAs, barrier one after the
+// other (profiles/linear_stream_deep.md).  This one is the same arithmetic on
+//
+//   * 256 rows x all N <= 256 columns per block: 16 waves (4 x 4, the same
+//     64x64 sub-tile each), one block per CU.  W is staged once per 256 rows;
+//   * 32-deep slabs, A through a ring of five and W through a ring of three
+//     (128 KB of LDS).  Step s multiplies slab s from registers, reads the
+//     fragments of slab s+1 under those MFMAs (each into the registers its
+//     last MFMA of the step has just freed: one fragment set, 128 VGPRs),
+//     issues W(s+3) then A(s+5) into the slots slab s left in step s-1, and
+//     ends on a counted wait for slab s+2 and the step's one barrier: three
+//     slabs of A stay in flight across it;
+//   * KEY is the image's slot key (mfma_tile.h).  A key that also separates
+//     rows r and r+4 measured the same (profiles/linear_stream_deep.md) and
+//     was dropped.
+//
+// Ring slots are compile-time constants in every step (15 steps unrolled, the
+// rings' common period), so the compiler can tell the DMA targets from the
+// images the fragment reads use and puts no full wait in front of the MFMAs.
+// Epilogue, edges and bits are those of the kernel above.
+
+#define LD_THREADS 1024
+#define LD_WAVES 16
+#define LD_BM 256
+#define LD_BK 32
+#define LD_NA 5
+#define LD_NW 3
+
+template <int EPI, typename KEY>
+__global__ __launch_bounds__(LD_THREADS, 4) void linear_stream_deep_kernel(
+    const bf16raw* __restrict__ A, const bf16raw* __restrict__ B, bf16raw* __restrict__ C,
+    const float* __restrict__ bias, int M, int N, int K) {
+  constexpr int BKT = LD_BK;
+  constexpr int A_EL = LD_BM * BKT, B_EL = LS_BN * BKT;
+  constexpr int EP_EL = LD_WAVES * 16 * MT_EPAD * 2;  // epilogue scratch, in bf16 units
+  constexpr int ST_EL = LD_NA * A_EL + LD_NW * B_EL;
+  static_assert(LD_BM * BKT * 2 / 1024 == LD_WAVES && LS_BN * BKT * 2 / 1024 == LD_WAVES,
+                "one DMA instruction per wave and slab: publish() counts them");
+  static_assert(ST_EL >= EP_EL, "the epilogue's scratch reuses the rings");
+  __shared__ __attribute__((aligned(16))) bf16raw smem[ST_EL];
+#define LD_B(i) (smem + ((i) % LD_NW) * B_EL)
+#define LD_A(i) (smem + LD_NW * B_EL + ((i) % LD_NA) * A_EL)
+
+  const int t = threadIdx.x;
+  const int wid = __builtin_amdgcn_readfirstlane(t >> 6), lane = t & 63;
+  const int wr = wid >> 2, wc = wid & 3;
+  const int l15 = lane & 15, kg = lane >> 4;
+  const int64_t m0 = (int64_t)blockIdx.x * LD_BM;
+  const bool rows_full = m0 + LD_BM <= M;
+  const bool active = wc * 64 < N;  // N = 192: wave column 3 has no outputs
+
+  // Both images are 256 rows x 4 slots and a wave's 1 KB DMA chunk is 16 rows,
+  // so thread t stages the 16 B at image offset t * 16 whether by DMA or by
+  // the guarded copy: image row t / 4, whose source k-slot the key picks.
+  // One 32-bit byte offset per operand, added to a wave-uniform slab address,
+  // keeps the address registers few (K <= 65536 bounds it).  W's image rows
+  // at or past N get copies of valid rows by DMA, so every wave issues one.
+  const int srow = t >> 2;
+  const int sk = ((lane & 3) ^ KEY::template key<4>(srow)) << 3;
+  const uint32_t a_off = (uint32_t)(srow * K + sk) * 2;
+  const uint32_t b_off = (uint32_t)((srow < N ? srow : (srow & 63)) * K + sk) * 2;
+  const char* const a_tile = (const char*)(A + m0 * K);
+
+  // 1 when the slab went by DMA (one instruction per wave, in flight), else 0
+  auto stage_a = [&](bf16raw* an, int kt) -> int {
+    const char* src = a_tile + kt * 2;
+    if (rows_full && kt + BKT <= K) {
+      mt_glds16((const bf16raw*)(src + a_off), an + wid * 512);
+      return 1;
+    }
+    shortx8 v = {};
+    if (m0 + srow < M && kt + sk < K) v = *(const shortx8*)(src + a_off);
+    *(shortx8*)(an + t * 8) = v;
+    return 0;
+  };
+  auto stage_b = [&](bf16raw* bn, int kt) -> int {
+    const char* src = (const char*)(B + kt);
+    if (kt + BKT <= K) {
+      mt_glds16((const bf16raw*)(src + b_off), bn + wid * 512);
+      return 1;
+    }
+    shortx8 v = {};
+    if (srow < N && kt + sk < K) v = *(const shortx8*)(src + b_off);
+    *(shortx8*)(bn + t * 8) = v;
+    return 0;
+  };
+  // the wave's memory instructions other than its newest `newer` are complete
+  auto publish = [&](int newer) {
+    switch (newer) {
+      case 4: mt_wait_barrier<4>(); break;
+      case 3: mt_wait_barrier<3>(); break;
+      case 2: mt_wait_barrier<2>(); break;
+      case 1: mt_wait_barrier<1>(); break;
+      default: mt_wait_barrier<0>(); break;
+    }
+  };
+
+  floatx4 acc[4][4] = {};
+  mt_frag_t a[4], b[4];
+  auto ld_a = [&](const bf16raw* ab, int mi) {
+    return mt_ld_frag32<KEY>(ab, wr * 64 + mi * 16 + l15, kg);
+  };
+  auto ld_b = [&](const bf16raw* bb, int ni) {
+    return mt_ld_frag32<KEY>(bb, wc * 64 + ni * 16 + l15, kg);
+  };
+
+  // K > 256: slabs 0 .. 4 of A and 0 .. 2 of W exist and only A can need the
+  // guarded stage (rows past M).  Issue order: everything slabs 0 and 1 need,
+  // then A2 A3 W2 A4; the wait leaves those four in flight.
+  int a_last = 0;  // A(s+4) of the step before went by DMA
+  {
+    int newer = 0;
+    stage_a(LD_A(0), 0);
+    stage_b(LD_B(0), 0);
+    stage_a(LD_A(1), BKT);
+    stage_b(LD_B(1), BKT);
+    newer += stage_a(LD_A(2), 2 * BKT);
+    newer += stage_a(LD_A(3), 3 * BKT);
+    newer += stage_b(LD_B(2), 2 * BKT);
+    newer += a_last = stage_a(LD_A(4), 4 * BKT);
+    publish(newer);
+  }
+  if (active) {
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      a[i] = ld_a(LD_A(0), i);
+      b[i] = ld_b(LD_B(0), i);
+    }
+  }
+  // slot 0 of both rings is the first DMA target below
+  mt_lds_barrier();
+
+  // Step on slab kt (in a / b); `an`, `bn` hold slab kt + BKT, published by
+  // the step before; `ai`, `bi` held slab kt, last read in the step before.
+  // At its end slab kt + 2 BKT must have landed: W of it was issued in the
+  // step before, ahead of that step's A, so what may stay in flight is that A
+  // and this step's two issues.
+  auto step = [&](const bf16raw* an, const bf16raw* bn, bf16raw* ai, bf16raw* bi, int kt) {
+    int newer = a_last;
+    if (kt + LD_NW * BKT < K) newer += stage_b(bi, kt + LD_NW * BKT);
+    a_last = 0;
+    if (kt + LD_NA * BKT < K) newer += a_last = stage_a(ai, kt + LD_NA * BKT);
+    if (active) {
+      // Each fragment of slab kt + BKT goes into the registers its last MFMA
+      // of this step has just freed: a[mi] after row mi, b[ni] inside the
+      // last row.  Past the last slab these read a stale image, unused.
+#pragma unroll
+      for (int mi = 0; mi < 4; ++mi) {
+#pragma unroll
+        for (int ni = 0; ni < 4; ++ni) {
+          acc[mi][ni] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[mi], b[ni], acc[mi][ni], 0, 0, 0);
+          if (mi == 3) b[ni] = ld_b(bn, ni);
+        }
+        a[mi] = ld_a(an, mi);
+      }
+    }
+    publish(newer);
+  };
+
+  for (int kt = 0;; kt += 15 * BKT) {
+#define LD_STEP(j)                                                                \
+  step(LD_A(j + 1), LD_B(j + 1), LD_A(j), LD_B(j), kt + (j) * BKT);               \
+  if (kt + ((j) + 1) * BKT >= K) break;
+    LD_STEP(0) LD_STEP(1) LD_STEP(2) LD_STEP(3) LD_STEP(4)
+    LD_STEP(5) LD_STEP(6) LD_STEP(7) LD_STEP(8) LD_STEP(9)
+    LD_STEP(10) LD_STEP(11) LD_STEP(12) LD_STEP(13) LD_STEP(14)
+#undef LD_STEP
+  }
+#undef LD_A
+#undef LD_B
+
+  // Epilogue, as above: the last step waited for everything and its barrier
+  // left the rings idle.
+  if (!active) return;
+  const int64_t m_base = m0 + wr * 64;
+  const int n_base = wc * 64;
+  float* ep = (float*)smem + wid * MT_EP_FLOATS;
+#pragma unroll
+  for (int mi = 0; mi < 4; ++mi) {
+    const int64_t m = m_base + mi * 16 + (lane >> 2);
+    mt_epi_slice<EPI>(ep, acc[mi], lane, l15, kg, m < M, m, N, n_base, C, bias, nullptr);
+  }
+}
+
+// 1 when the deep-K forward serves this shape
+extern "C" int linear_fwd_stream_deep_supported(int N, int K, int64_t M) {
+  return N > 128 && N <= LS_BN && N % 64 == 0 && K > 256 && K <= 65536 && K % 8 == 0 && M >= 1 &&
+         M < (1LL << 31) - LD_BM;
+}
+
 // 1 when the kernel can compute C[M,N] = A[M,K] B for this shape
 extern "C" int linear_fwd_stream_supported(int N, int K, int64_t M) {
   return N > 128 && N <= LS_BN && N % 64 == 0 && K >= 8 && K % 8 == 0 && M >= 1 &&
@@ -265,13 +458,26 @@ extern "C" int linear_fwd_stream_supported(int N, int K, int64_t M) {
 #define LS_MIN_ROWS 32768
 extern "C" int64_t linear_fwd_stream_min_rows() { return LS_MIN_ROWS; }
 
+// Rows from which the automatic choice gives a K > 256 forward to the deep
+// kernel: the smallest M at which tools/linear_stream_bench.hip measured it
+// not slower than the kernel above at 784 -> 256
+// (profiles/linear_stream_deep.md, "Threshold").  Its grid is one 256-row
+// block per CU, which loses while the blocks do not fill the chip.
+#define LS_DEEP_MIN_ROWS 65536
+extern "C" int64_t linear_fwd_stream_deep_min_rows() { return LS_DEEP_MIN_ROWS; }
+
+#define LS_PATH_AUTO 0
+#define LS_PATH_TILE128 1  // linear_stream_kernel
+#define LS_PATH_DEEP 2     // linear_stream_deep_kernel
+
 // epi: EPI_BF16 / BIAS / BIAS_RELU / RELU (mfma_tile.h) for the forward
 // (b_kn = 0, B = W[N][K]); EPI_BF16 / EPI_BF16_MASK for the dgrad (b_kn = 1,
-// B = W[K][N]).  bk: k-slab depth 32 or 64, 0 = the measured default.  All
-// pointers 16-byte aligned.
+// B = W[K][N]).  bk: k-slab depth of linear_stream_kernel, 32 or 64, 0 = the
+// measured default.  fwd_path: which forward kernel, LS_PATH_*; the dgrad has
+// one.  All pointers 16-byte aligned.
 extern "C" hipError_t launch_linear_stream(const bf16raw* A, const bf16raw* B, bf16raw* C,
                                            const float* bias, const bf16raw* mask, int64_t M,
-                                           int N, int K, int epi, int b_kn, int bk,
+                                           int N, int K, int epi, int b_kn, int bk, int fwd_path,
                                            hipStream_t stream) {
   if (!linear_fwd_stream_supported(N, K, M)) return hipErrorInvalidValue;
   if ((((uintptr_t)A) | ((uintptr_t)B) | ((uintptr_t)C) | ((uintptr_t)mask)) & 15)
@@ -281,6 +487,26 @@ extern "C" hipError_t launch_linear_stream(const bf16raw* A, const bf16raw* B, b
   if (epi == EPI_BF16_MASK && mask == nullptr) return hipErrorInvalidValue;
   if (bk == 0) bk = 32;
   if (bk != 32 && bk != 64) return hipErrorInvalidValue;
+  if (fwd_path < LS_PATH_AUTO || fwd_path > LS_PATH_DEEP) return hipErrorInvalidValue;
+  if (fwd_path == LS_PATH_AUTO)
+    fwd_path = !b_kn && M >= LS_DEEP_MIN_ROWS && linear_fwd_stream_deep_supported(N, K, M)
+                   ? LS_PATH_DEEP
+                   : LS_PATH_TILE128;
+  if (fwd_path == LS_PATH_DEEP) {
+    if (b_kn || !linear_fwd_stream_deep_supported(N, K, M)) return hipErrorInvalidValue;
+    const dim3 dgrid((unsigned)ceil_div_i64(M, LD_BM)), dblock(LD_THREADS);
+#define LS_LAUNCH_DEEP(EPIC)                                                     \
+  linear_stream_deep_kernel<EPIC, mt_key_row><<<dgrid, dblock, 0, stream>>>(     \
+      A, B, C, bias, (int)M, N, K)
+    if (epi == EPI_BF16) LS_LAUNCH_DEEP(EPI_BF16);
+    else if (epi == EPI_BIAS) LS_LAUNCH_DEEP(EPI_BIAS);
+    else if (epi == EPI_BIAS_RELU) LS_LAUNCH_DEEP(EPI_BIAS_RELU);
+    else if (epi == EPI_RELU) LS_LAUNCH_DEEP(EPI_RELU);
+    else return hipErrorInvalidValue;
+#undef LS_LAUNCH_DEEP
+    HIP_CHECK_LAUNCH();
+    return hipSuccess;
+  }
   const dim3 grid((unsigned)ceil_div_i64(M, LS_BM)), block(LS_THREADS);
 #define LS_LAUNCH(EPIC, BT)                                                                   \
   do {                                                                                        \

@@ -69,6 +69,15 @@ __device__ __forceinline__ void mt_glds16(const bf16raw* g, bf16raw* lds) {
                                    (__attribute__((address_space(3))) unsigned int*)lds, 16, 0, 0);
 }
 
+// Slot keys of the k-major image: image slot = source slot ^ KEY::key(row).
+// mt_key_row is the image described at the top of this file.
+struct mt_key_row {
+  template <int SLOTS>
+  static __device__ __forceinline__ int key(int row) {
+    return row & (SLOTS - 1);
+  }
+};
+
 // k-contiguous operand src[row0 + row][kt ..] (row stride ld) -> k-major image.
 // Source rows row0 .. row0 + nrows - 1 must exist; nrows is a multiple of 16.
 // PAD_ROWS = false: chunks past nrows are skipped.
@@ -76,7 +85,7 @@ __device__ __forceinline__ void mt_glds16(const bf16raw* g, bf16raw* lds) {
 // valid rows (never read), so that every wave issues the same
 // ROWS * BKT * 2 / 1024 / WAVES instructions whatever nrows is.
 // mlp_predict_kernel's counted waits rely on it.
-template <int WAVES, int ROWS, int BKT, bool PAD_ROWS>
+template <int WAVES, int ROWS, int BKT, bool PAD_ROWS, typename KEY = mt_key_row>
 __device__ __forceinline__ void mt_dma_kmajor(const bf16raw* __restrict__ src,
                                               bf16raw* __restrict__ lds, int64_t row0, int nrows,
                                               int64_t ld, int kt, int wid, int lane) {
@@ -92,7 +101,7 @@ __device__ __forceinline__ void mt_dma_kmajor(const bf16raw* __restrict__ src,
     if (PAD_ROWS || c * CH_ROWS < nrows) {
       const int row = c * CH_ROWS + r_in;
       const int srow = PAD_ROWS ? (row < nrows ? row : (row & 63)) : row;
-      const int sslot = slot ^ (row & (SLOTS - 1));
+      const int sslot = slot ^ KEY::template key<SLOTS>(row);
       const bf16raw* g = src + (row0 + srow) * ld + kt + sslot * 8;
       mt_glds16(g, lds + c * CH_ROWS * BKT);
     }
@@ -101,7 +110,7 @@ __device__ __forceinline__ void mt_dma_kmajor(const bf16raw* __restrict__ src,
 
 // the same image with zero fill: rows at or past rmax, k at or past kmax
 // (K is a multiple of 8, so a slot is wholly inside or wholly outside)
-template <int THREADS, int ROWS, int BKT>
+template <int THREADS, int ROWS, int BKT, typename KEY = mt_key_row>
 __device__ __forceinline__ void mt_fill_kmajor(const bf16raw* __restrict__ src,
                                                bf16raw* __restrict__ lds, int64_t row0,
                                                int64_t rmax, int ld, int kt, int kmax, int t) {
@@ -109,7 +118,7 @@ __device__ __forceinline__ void mt_fill_kmajor(const bf16raw* __restrict__ src,
 #pragma unroll
   for (int u = t; u < ROWS * SLOTS; u += THREADS) {
     const int row = u / SLOTS;
-    const int k = kt + (((u % SLOTS) ^ (row & (SLOTS - 1))) << 3);
+    const int k = kt + (((u % SLOTS) ^ KEY::template key<SLOTS>(row)) << 3);
     shortx8 v = {};
     if (row0 + row < rmax && k < kmax) v = *(const shortx8*)(src + (row0 + row) * ld + k);
     *(shortx8*)(lds + u * 8) = v;
@@ -123,6 +132,12 @@ __device__ __forceinline__ void mt_fill_kmajor(const bf16raw* __restrict__ src,
 template <int STRIDE, int XM>
 __device__ __forceinline__ mt_frag_t mt_ld_frag(const bf16raw* img, int row, int slot) {
   return *(const mt_frag_t*)&img[row * STRIDE + ((slot ^ (row & XM)) << 3)];
+}
+
+// the same read of a 32-deep k-major image staged with slot key KEY
+template <typename KEY>
+__device__ __forceinline__ mt_frag_t mt_ld_frag32(const bf16raw* img, int row, int slot) {
+  return *(const mt_frag_t*)&img[row * 32 + ((slot ^ KEY::template key<4>(row)) << 3)];
 }
 
 // Transposing read (ds_read_b64_tr_b16) of an image stored as it lies in

@@ -75,7 +75,7 @@ int main(int argc, char** argv) {
           CKB(hipMemset(db[r], 0, No * 4));
         }
         if (v == 0)
-          CKB(launch_linear_stream(dz, w, o[0], nullptr, x, B, Ki, No, EPI_BF16_MASK, 1, 0, 0));
+          CKB(launch_linear_stream(dz, w, o[0], nullptr, x, B, Ki, No, EPI_BF16_MASK, 1, 0, 0, 0));
         else if (v == 1)
           CKB(launch_linear_wgrad_stream(dz, x, dw[0], db[0], B, No, Ki, 0, cus, 0));
         else

@@ -1,5 +1,6 @@
 // Microbench: full-N streaming Linear forward / dgrad+mask (linear_stream.hip)
-// against gemm_kernel's 128x128-tile route (gemm.hip) at the flagship shapes.
+// against gemm_kernel's 128x128-tile route (gemm.hip) at the flagship shapes;
+// at K > 256 also the deep-K forward (linear_stream_deep_kernel).
 // hipcc --offload-arch=gfx950 -O3 -ffast-math tools/linear_stream_bench.hip -o tools/linear_stream_bench
 // usage: linear_stream_bench [M ...]      (default 2097152)
 // Prints us and TB/s of NEEDED bytes (A once + C once (+ mask once)), and
@@ -32,23 +33,26 @@ int main(int argc, char** argv) {
       {"fwd   784->256", 784, 256, 0}, {"fwd   256->256", 256, 256, 0},
       {"dgrad 256->256", 256, 256, 1}};
   const int WARM = 2, REPS = 10;
+  constexpr int NV = 4;
   for (int64_t M : ms)
     for (auto& s : shapes) {
-      bf16raw *a, *w, *mask, *c[3]; float* bias;
+      bf16raw *a, *w, *mask, *c[NV]; float* bias;
       CKB(hipMalloc(&a, M * s.K * 2));
       CKB(hipMalloc(&w, (size_t)s.K * s.N * 2));
       CKB(hipMalloc(&mask, M * s.N * 2));
       CKB(hipMalloc(&bias, s.N * 4));
-      for (int v = 0; v < 3; ++v) CKB(hipMalloc(&c[v], M * s.N * 2));
+      for (int v = 0; v < NV; ++v) CKB(hipMalloc(&c[v], M * s.N * 2));
       fill_kernel<<<2048, 256>>>(a, M * s.K, 1u, !s.dgrad, 1.f);
       fill_kernel<<<64, 256>>>(w, (int64_t)s.K * s.N, 2u, 0, 0.0625f);
       fill_kernel<<<2048, 256>>>(mask, M * s.N, 3u, 1, 1.f);
       CKB(hipMemset(bias, 0, s.N * 4));
       CKB(hipDeviceSynchronize());
       hipEvent_t e0, e1; CKB(hipEventCreate(&e0)); CKB(hipEventCreate(&e1));
-      float us[3];
-      const char* names[3] = {"gemm 128x128", "stream BK=32", "stream BK=64"};
-      for (int v = 0; v < 3; ++v) {
+      float us[NV];
+      const char* names[NV] = {"gemm 128x128", "stream BK=32", "stream BK=64", "deep 256 rows"};
+      const bool deep = !s.dgrad && linear_fwd_stream_deep_supported(s.N, s.K, M);
+      const int nv = deep ? NV : 3;
+      for (int v = 0; v < nv; ++v) {
         for (int it = 0; it < WARM + REPS; ++it) {
           if (it == WARM) CKB(hipEventRecord(e0));
           if (v == 0) {
@@ -62,7 +66,8 @@ int main(int argc, char** argv) {
             CKB(launch_linear_stream(a, w, c[v], s.dgrad ? nullptr : bias,
                                      s.dgrad ? mask : nullptr, M, s.N, s.K,
                                      s.dgrad ? EPI_BF16_MASK : EPI_BIAS_RELU, s.dgrad,
-                                     v == 1 ? 32 : 64, 0));
+                                     v == 2 ? 64 : 32, v == 3 ? LS_PATH_DEEP : LS_PATH_TILE128,
+                                     0));
           }
         }
         CKB(hipEventRecord(e1)); CKB(hipEventSynchronize(e1));
@@ -71,9 +76,9 @@ int main(int argc, char** argv) {
       }
       // bit comparison on a prefix and a suffix (the whole C at small M)
       const size_t total = (size_t)M * s.N, chunk = total < (1u << 22) ? total : (1u << 22);
-      bool same[3] = {true, true, true};
+      bool same[NV] = {true, true, true, true};
       std::vector<bf16raw> h0(chunk), h1(chunk);
-      for (int v = 1; v < 3; ++v)
+      for (int v = 1; v < nv; ++v)
         for (int part = 0; part < 2; ++part) {
           const size_t off = part ? total - chunk : 0;
           CKB(hipMemcpy(h0.data(), c[0] + off, chunk * 2, hipMemcpyDeviceToHost));
@@ -81,12 +86,12 @@ int main(int argc, char** argv) {
           if (memcmp(h0.data(), h1.data(), chunk * 2) != 0) same[v] = false;
         }
       const double bytes = (double)M * (s.K + s.N * (s.dgrad ? 2 : 1)) * 2;
-      for (int v = 0; v < 3; ++v)
+      for (int v = 0; v < nv; ++v)
         printf("M=%8ld %s %-12s: %8.1f us  %5.2f TB/s needed  %6.1f TF/s%s\n", (long)M, s.name,
                names[v], us[v], bytes / us[v] / 1e6, 2.0 * M * s.K * s.N / us[v] / 1e6,
                v == 0 ? "" : (same[v] ? "  bits==gemm" : "  BITS DIFFER"));
       hipFree(a); hipFree(w); hipFree(mask); hipFree(bias);
-      for (int v = 0; v < 3; ++v) hipFree(c[v]);
+      for (int v = 0; v < NV; ++v) hipFree(c[v]);
     }
   return 0;
 }

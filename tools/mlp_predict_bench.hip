@@ -91,7 +91,7 @@ int main(int argc, char** argv) {
           const bf16raw* in = l == 0 ? x : act[l - 1];
           const int epi = l < L ? EPI_BIAS_RELU : EPI_BIAS;
           if (linear_fwd_stream_supported(N, K, M) && M >= LS_MIN_ROWS)
-            CKB(launch_linear_stream(in, w[l], act[l], b[l], nullptr, M, N, K, epi, 0, 0, 0));
+            CKB(launch_linear_stream(in, w[l], act[l], b[l], nullptr, M, N, K, epi, 0, 0, 0, 0));
           else
             CKB(launch_gemm_bf16(in, w[l], 0, nullptr, act[l], b[l], (int)M, N, K, K, 1, 1, K, epi, 1,
                                  nullptr, -1, 0));
