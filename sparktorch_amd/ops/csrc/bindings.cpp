@@ -67,6 +67,8 @@ hipError_t launch_head_bwd(const bf16raw*, const bf16raw*, const bf16raw*, bf16r
                            float*, int, int, int, int, int, hipStream_t);
 hipError_t launch_head_ce(const bf16raw*, const float*, const bf16raw*, const int64_t*, bf16raw*,
                           float*, float*, float*, bf16raw*, int, int, int, int, int, hipStream_t);
+hipError_t launch_head_mse(const bf16raw*, const float*, const bf16raw*, const bf16raw*, bf16raw*,
+                           float*, float*, float*, bf16raw*, int, int, int, int, int, hipStream_t);
 int mlp_predict_supported(int, const int*, int, int, int64_t);
 int64_t mlp_predict_min_rows();
 hipError_t launch_mlp_predict(const bf16raw*, const bf16raw* const*, const float* const*,
@@ -652,6 +654,47 @@ std::tuple<at::Tensor, at::Tensor, at::Tensor> linear_head_ce(
                            want_logits ? (bf16raw*)logits.data_ptr() : nullptr, (int)B, (int)C,
                            (int)H, (int)max_blocks, head_num_cus(), cur_stream()));
   return {loss, dz_in, logits};
+}
+
+// The regression twin (head_bwd.hip, head_mse_kernel): mean squared error
+// against a bf16 [B, C] target; returns (loss, dz_in, pred or an empty tensor).
+std::tuple<at::Tensor, at::Tensor, at::Tensor> linear_head_mse(
+    at::Tensor y_in, at::Tensor w, c10::optional<at::Tensor> bias, at::Tensor target,
+    at::Tensor dw, c10::optional<at::Tensor> db, bool want_pred, int64_t max_blocks) {
+  check_gpu_contig(y_in, at::kBFloat16, "y_in");
+  check_gpu_contig(w, at::kBFloat16, "w");
+  check_gpu_contig(target, at::kBFloat16, "target");
+  check_gpu_contig(dw, at::kFloat, "dw");
+  TORCH_CHECK(y_in.dim() == 2 && w.dim() == 2 && target.dim() == 2);
+  int64_t B = y_in.size(0), H = y_in.size(1), C = w.size(0);
+  TORCH_CHECK(B >= 1 && B < (1LL << 31) && w.size(1) == H && target.size(0) == B &&
+                  target.size(1) == C && dw.dim() == 2 && dw.size(0) == C && dw.size(1) == H,
+              "shape mismatch");
+  TORCH_CHECK(head_bwd_ok(C, H), "linear_head_mse: unsupported (C, H); use the three-step route");
+  const float* bp = nullptr;
+  if (bias.has_value()) {
+    check_gpu_contig(*bias, at::kFloat, "bias");
+    TORCH_CHECK(bias->numel() == C);
+    bp = bias->data_ptr<float>();
+  }
+  float* dbp = nullptr;
+  if (db.has_value()) {
+    check_gpu_contig(*db, at::kFloat, "db");
+    TORCH_CHECK(db->numel() == C);
+    dbp = db->data_ptr<float>();
+  }
+  auto loss = at::empty({}, y_in.options().dtype(at::kFloat));
+  auto dz_in = at::empty({B, H}, y_in.options());
+  auto pred = want_pred ? at::empty({B, C}, y_in.options()) : at::empty({0}, y_in.options());
+  TORCH_CHECK(((uintptr_t)y_in.data_ptr() & 15) == 0 && ((uintptr_t)dz_in.data_ptr() & 15) == 0 &&
+                  ((uintptr_t)w.data_ptr() & 15) == 0,
+              "linear_head_mse wants 16-byte aligned activations and weights");
+  CHECK_HIP(launch_head_mse((const bf16raw*)w.data_ptr(), bp, (const bf16raw*)y_in.data_ptr(),
+                            (const bf16raw*)target.data_ptr(), (bf16raw*)dz_in.data_ptr(),
+                            dw.data_ptr<float>(), dbp, loss.data_ptr<float>(),
+                            want_pred ? (bf16raw*)pred.data_ptr() : nullptr, (int)B, (int)C,
+                            (int)H, (int)max_blocks, head_num_cus(), cur_stream()));
+  return {loss, dz_in, pred};
 }
 
 // Whole-MLP inference in one launch (mlp_predict.hip): x through the hidden
@@ -1416,6 +1459,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "head forward + cross-entropy + one-pass head backward: (loss, dz_in, logits)",
         py::arg("y_in"), py::arg("w"), py::arg("bias"), py::arg("target"), py::arg("dw"),
         py::arg("db"), py::arg("want_logits") = false, py::arg("max_blocks") = 0);
+  m.def("linear_head_mse", &linear_head_mse,
+        "head forward + mean squared error + one-pass head backward: (loss, dz_in, pred)",
+        py::arg("y_in"), py::arg("w"), py::arg("bias"), py::arg("target"), py::arg("dw"),
+        py::arg("db"), py::arg("want_pred") = false, py::arg("max_blocks") = 0);
   m.def("mlp_predict_supported", &mlp_predict_ok,
         "does the one-launch MLP inference kernel serve (K0, hidden widths, C)");
   m.def("mlp_predict_min_rows", &mlp_predict_min_rows_py,

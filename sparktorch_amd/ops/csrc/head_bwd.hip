@@ -40,6 +40,15 @@
 // image and the two stages above run unchanged.  The head's forward, the
 // loss and the head's backward then read y_in once and the logits never reach
 // HBM (profiles/head_ce.md).
+//
+// head_mse_kernel is the regression twin, for a train step under mean squared
+// error against a bf16 [B, C] target: the same forward gives pred, the per-row
+// softmax is replaced by loss.hip's mse arithmetic (d = pred - target,
+// dpred = 2 d / (B C)), and dpred goes into the dz image the same way.  A
+// lane's four target values (its class column, the four rows whose pred it
+// receives) are fetched into registers one tile ahead, where head_ce_kernel
+// fetches its class ids, so they arrive under the y_in DMA and never pass
+// through LDS (profiles/head_mse.md).
 
 #include "mfma_tile.h"
 
@@ -54,16 +63,23 @@ struct head_key {
   static __device__ __forceinline__ int key(int row) { return row & XM; }
 };
 
-// Tile loop shared by head_bwd_kernel (CE = false: the dz_out image is staged
-// from global memory) and head_ce_kernel (CE = true: the image is computed
-// from the resident y_in tile; dz_out is unused).
-template <int H, bool CE>
+// Tile loop shared by head_bwd_kernel (HEAD_BWD: the dz_out image is staged
+// from global memory), head_ce_kernel and head_mse_kernel (HEAD_CE, HEAD_MSE:
+// the image is computed from the resident y_in tile; dz_out is unused).  tgt
+// is int64 [B] class ids for HEAD_CE and bf16 [B, C] values for HEAD_MSE;
+// scale is 1 / B and 1 / (B C).
+#define HEAD_BWD 0
+#define HEAD_CE 1
+#define HEAD_MSE 2
+
+template <int H, int MODE>
 __device__ __forceinline__ void head_tiles(
     const bf16raw* __restrict__ dz_out, const bf16raw* __restrict__ w,
     const bf16raw* __restrict__ y_in, bf16raw* __restrict__ dz_in, float* __restrict__ dw,
     float* __restrict__ db, int B, int C, const float* __restrict__ bias,
-    const int64_t* __restrict__ tgt, float* __restrict__ loss, bf16raw* __restrict__ logits_out,
+    const void* __restrict__ tgt, float* __restrict__ loss, bf16raw* __restrict__ logits_out,
     float inv_B) {
+  constexpr bool FWD = MODE != HEAD_BWD;  // the forward + loss stage is present
   constexpr int ROWS = head_rows(H);
   constexpr int SLOTS = H / 8;                     // 16 B slots per image row
   constexpr int XM = (SLOTS % 16 == 0) ? 15 : 7;   // slot ^= row & XM
@@ -74,8 +90,9 @@ __device__ __forceinline__ void head_tiles(
   static_assert(H % 64 == 0 && H <= 512, "unsupported H");
 
   __shared__ __attribute__((aligned(16))) bf16raw ys[2][ROWS * H];
-  // CE fills and consumes the dz image inside one tile step: one buffer
-  __shared__ __attribute__((aligned(16))) bf16raw dzs[CE ? 1 : 2][ROWS * HEAD_CPAD];
+  // the forward modes fill and consume the dz image inside one tile step: one
+  // buffer
+  __shared__ __attribute__((aligned(16))) bf16raw dzs[FWD ? 1 : 2][ROWS * HEAD_CPAD];
 
   const int t = threadIdx.x;
   const int wid = t >> 6, lane = t & 63;
@@ -105,22 +122,28 @@ __device__ __forceinline__ void head_tiles(
   floatx4 accw[PW][2] = {};
   floatx4 accb = {0.f, 0.f, 0.f, 0.f};
 
-  // CE: w again as the forward's B operand, the lane's bias, next tile's
-  // targets and the block's loss
+  // CE / MSE: w again as the forward's B operand, the lane's bias, next
+  // tile's targets (class ids, or the bits of bf16 values) and the block's loss
   mt_frag_t wk[H / 32];
   float bias_c = 0.f, lsum = 0.f;
   int tg[4] = {0, 0, 0, 0};
-  if (CE) {
+  if (FWD) {
     mt_head_w_frags(wk, w, H, C, l15, q);
     if (bias != nullptr && l15 < C) bias_c = bias[l15];
   }
   // targets of the rows whose logits this lane receives (wave wid owns tile
-  // rows wid*16 .. +15; accumulator element r <-> row wid*16 + q*4 + r)
+  // rows wid*16 .. +15; accumulator element r <-> row wid*16 + q*4 + r); MSE:
+  // those rows' values in the lane's own column l15
   auto load_tgt = [&](int tile) {
     if (wid < ROWS / 16) {
       const int64_t gr = (int64_t)tile * ROWS + wid * 16 + q * 4;
 #pragma unroll
-      for (int r = 0; r < 4; ++r) tg[r] = (gr + r < B) ? (int)tgt[gr + r] : 0;
+      for (int r = 0; r < 4; ++r) {
+        if (MODE == HEAD_MSE)
+          tg[r] = (gr + r < B && l15 < C) ? (int)((const bf16raw*)tgt)[(gr + r) * C + l15] : 0;
+        else
+          tg[r] = (gr + r < B) ? (int)((const int64_t*)tgt)[gr + r] : 0;
+      }
     }
   };
 
@@ -156,7 +179,7 @@ __device__ __forceinline__ void head_tiles(
   int buf = 0;
   if (tile < ntiles) {
     dma_y(0, tile);
-    if (CE) {
+    if (FWD) {
       load_tgt(tile);
     } else {
       load_dz(tile);
@@ -165,16 +188,16 @@ __device__ __forceinline__ void head_tiles(
   }
   for (; tile < ntiles; tile += gridDim.x) {
     // tile's images are complete and every wave is done with the other pair
-    // (CE says so itself: each wave's DMA of this tile has landed)
-    if (CE)
+    // (a forward mode says so itself: each wave's DMA of this tile has landed)
+    if (FWD)
       mt_wait_barrier<0>();
     else
       __syncthreads();
     const int next = tile + gridDim.x;
     const bf16raw* yb = ys[buf];
-    bf16raw* zb = dzs[CE ? 0 : buf];
+    bf16raw* zb = dzs[FWD ? 0 : buf];
     const int64_t row0 = (int64_t)tile * ROWS;
-    if (CE) {
+    if (FWD) {
       int tc[4];
 #pragma unroll
       for (int r = 0; r < 4; ++r) tc[r] = tg[r];
@@ -195,56 +218,73 @@ __device__ __forceinline__ void head_tiles(
 #pragma clang fp reassociate(off)  // the class sums keep loss.hip's order
         const floatx4 lg = EARLY ? mt_head_logits(ay, wk)
                                  : mt_head_logits<H / 32, H, XM>(wk, yb, arow, H, q);
-        // lane (class l15, q), element r <-> tile row wid*16 + q*4 + r.  The
-        // per-row arithmetic is loss.hip's; RG rows go side by side so their
-        // lane exchanges overlap (H = 512 has the registers for one).
-        constexpr int RG = H <= 256 ? 4 : 1;
+        if (MODE == HEAD_MSE) {
+          // lane (column l15, q), element r <-> tile row wid*16 + q*4 + r:
+          // mse_fused_kernel's arithmetic on that one element
 #pragma unroll
-        for (int r0 = 0; r0 < 4; r0 += RG) {
-          bf16raw xb[RG];
-          float x[RG], mx[RG], e[RG], se[RG];
-#pragma unroll
-          for (int j = 0; j < RG; ++j) {
-            xb[j] = f32_to_bf16(bias != nullptr ? lg[r0 + j] + bias_c : lg[r0 + j]);
-            x[j] = bf16_to_f32(xb[j]);
-            mx[j] = l15 < C ? fmaxf(-1e30f, x[j]) : -1e30f;
+          for (int r = 0; r < 4; ++r) {
+            const int lrow = wid * 16 + q * 4 + r;
+            const bool live = row0 + lrow < B && l15 < C;
+            const bf16raw pb = f32_to_bf16(bias != nullptr ? lg[r] + bias_c : lg[r]);
+            const float d = bf16_to_f32(pb) - bf16_to_f32((bf16raw)tc[r]);
+            zb[lrow * HEAD_CPAD + l15] = live ? f32_to_bf16(2.f * d * inv_B) : (bf16raw)0;
+            if (live) {
+              lsum += d * d * inv_B;
+              if (logits_out != nullptr) logits_out[(row0 + lrow) * C + l15] = pb;
+            }
           }
+        } else {
+          // lane (class l15, q), element r <-> tile row wid*16 + q*4 + r.  The
+          // per-row arithmetic is loss.hip's; RG rows go side by side so their
+          // lane exchanges overlap (H = 512 has the registers for one).
+          constexpr int RG = H <= 256 ? 4 : 1;
 #pragma unroll
-          for (int off = 8; off; off >>= 1)
+          for (int r0 = 0; r0 < 4; r0 += RG) {
+            bf16raw xb[RG];
+            float x[RG], mx[RG], e[RG], se[RG];
 #pragma unroll
-            for (int j = 0; j < RG; ++j) mx[j] = fmaxf(mx[j], __shfl_xor(mx[j], off, 16));
-#pragma unroll
-          for (int j = 0; j < RG; ++j) e[j] = l15 < C ? __expf(x[j] - mx[j]) : 0.f;
-          if (B <= CE_WAVE_MAX_B) {  // ce_fused_wave_kernel's butterfly
-#pragma unroll
-            for (int j = 0; j < RG; ++j) se[j] = e[j];
+            for (int j = 0; j < RG; ++j) {
+              xb[j] = f32_to_bf16(bias != nullptr ? lg[r0 + j] + bias_c : lg[r0 + j]);
+              x[j] = bf16_to_f32(xb[j]);
+              mx[j] = l15 < C ? fmaxf(-1e30f, x[j]) : -1e30f;
+            }
 #pragma unroll
             for (int off = 8; off; off >>= 1)
 #pragma unroll
-              for (int j = 0; j < RG; ++j) se[j] += __shfl_xor(se[j], off, 16);
-          } else {  // ce_fused_kernel's class-ascending sum
+              for (int j = 0; j < RG; ++j) mx[j] = fmaxf(mx[j], __shfl_xor(mx[j], off, 16));
 #pragma unroll
-            for (int j = 0; j < RG; ++j) se[j] = 0.f;
-            for (int c = 0; c < C; ++c)
+            for (int j = 0; j < RG; ++j) e[j] = l15 < C ? __expf(x[j] - mx[j]) : 0.f;
+            if (B <= CE_WAVE_MAX_B) {  // ce_fused_wave_kernel's butterfly
 #pragma unroll
-              for (int j = 0; j < RG; ++j) se[j] += __shfl(e[j], c, 16);
-          }
+              for (int j = 0; j < RG; ++j) se[j] = e[j];
 #pragma unroll
-          for (int j = 0; j < RG; ++j) {
-            const int r = r0 + j;
-            const int lrow = wid * 16 + q * 4 + r;
-            const bool live = row0 + lrow < B;
-            const float xt = __shfl(x[j], tc[r] & 15, 16);
-            const float inv_se = 1.f / se[j];
-            // the target class in one fma: loss.hip's kernels compile to it
-            // under -ffast-math, and dz must keep their bits
-            const float p =
-                l15 == tc[r] ? __builtin_fmaf(e[j], inv_se, -1.f) : e[j] * inv_se;
-            zb[lrow * HEAD_CPAD + l15] =
-                (live && l15 < C) ? f32_to_bf16(p * inv_B) : (bf16raw)0;
-            if (live && l15 == 0) lsum += (__logf(se[j]) + mx[j] - xt) * inv_B;
-            if (logits_out != nullptr && live && l15 < C)
-              logits_out[(row0 + lrow) * C + l15] = xb[j];
+              for (int off = 8; off; off >>= 1)
+#pragma unroll
+                for (int j = 0; j < RG; ++j) se[j] += __shfl_xor(se[j], off, 16);
+            } else {  // ce_fused_kernel's class-ascending sum
+#pragma unroll
+              for (int j = 0; j < RG; ++j) se[j] = 0.f;
+              for (int c = 0; c < C; ++c)
+#pragma unroll
+                for (int j = 0; j < RG; ++j) se[j] += __shfl(e[j], c, 16);
+            }
+#pragma unroll
+            for (int j = 0; j < RG; ++j) {
+              const int r = r0 + j;
+              const int lrow = wid * 16 + q * 4 + r;
+              const bool live = row0 + lrow < B;
+              const float xt = __shfl(x[j], tc[r] & 15, 16);
+              const float inv_se = 1.f / se[j];
+              // the target class in one fma: loss.hip's kernels compile to it
+              // under -ffast-math, and dz must keep their bits
+              const float p =
+                  l15 == tc[r] ? __builtin_fmaf(e[j], inv_se, -1.f) : e[j] * inv_se;
+              zb[lrow * HEAD_CPAD + l15] =
+                  (live && l15 < C) ? f32_to_bf16(p * inv_B) : (bf16raw)0;
+              if (live && l15 == 0) lsum += (__logf(se[j]) + mx[j] - xt) * inv_B;
+              if (logits_out != nullptr && live && l15 < C)
+                logits_out[(row0 + lrow) * C + l15] = xb[j];
+            }
           }
         }
       }
@@ -304,11 +344,11 @@ __device__ __forceinline__ void head_tiles(
       }
     }
 
-    if (!CE && next < ntiles) write_dz(buf ^ 1);
+    if (!FWD && next < ntiles) write_dz(buf ^ 1);
     buf ^= 1;
   }
 
-  if (CE) {
+  if (FWD) {
     // one loss atomic per block
     __shared__ float lred[HEAD_THREADS / 64];
 #pragma unroll
@@ -345,7 +385,7 @@ __global__ __launch_bounds__(HEAD_THREADS, 2) void head_bwd_kernel(
     const bf16raw* __restrict__ dz_out, const bf16raw* __restrict__ w,
     const bf16raw* __restrict__ y_in, bf16raw* __restrict__ dz_in, float* __restrict__ dw,
     float* __restrict__ db, int B, int C) {
-  head_tiles<H, false>(dz_out, w, y_in, dz_in, dw, db, B, C, nullptr, nullptr, nullptr, nullptr,
+  head_tiles<H, HEAD_BWD>(dz_out, w, y_in, dz_in, dw, db, B, C, nullptr, nullptr, nullptr, nullptr,
                        0.f);
 }
 
@@ -360,9 +400,35 @@ __global__ __launch_bounds__(HEAD_THREADS, 2) void head_ce_kernel(
     const bf16raw* __restrict__ y_in, const int64_t* __restrict__ tgt,
     bf16raw* __restrict__ dz_in, float* __restrict__ dw, float* __restrict__ db,
     float* __restrict__ loss, bf16raw* __restrict__ logits_out, int B, int C, float inv_B) {
-  head_tiles<H, true>(nullptr, w, y_in, dz_in, dw, db, B, C, bias, tgt, loss, logits_out,
-                      inv_B);
+  head_tiles<H, HEAD_CE>(nullptr, w, y_in, dz_in, dw, db, B, C, bias, tgt, loss, logits_out,
+                         inv_B);
 }
+
+// Head forward + mean squared error (over B * C elements) + head backward in
+// one pass: with pred = y_in @ w^T + bias rounded to bf16 as above and
+// dz_out = d loss / d pred as mse_fused produces it,
+//   loss  += sum (pred - target)^2 / (B C)         (the launcher zeroes it)
+//   dz_in, dw, db as head_bwd_kernel; pred_out (nullable) gets pred.
+// This kernel alone is compiled without packed fp32 instructions (v_pk_*_f32);
+// the attribute means something to the device pass only.
+#ifdef __HIP_DEVICE_COMPILE__
+#define HEAD_NO_PK_F32 __attribute__((target("no-packed-fp32-ops")))
+#else
+#define HEAD_NO_PK_F32
+#endif
+
+template <int H>
+__global__ __launch_bounds__(HEAD_THREADS, 2) HEAD_NO_PK_F32 void head_mse_kernel(
+    const bf16raw* __restrict__ w, const float* __restrict__ bias,
+    const bf16raw* __restrict__ y_in, const bf16raw* __restrict__ target,
+    bf16raw* __restrict__ dz_in, float* __restrict__ dw, float* __restrict__ db,
+    float* __restrict__ loss, bf16raw* __restrict__ pred_out, int B, int C, float inv_n) {
+  head_tiles<H, HEAD_MSE>(nullptr, w, y_in, dz_in, dw, db, B, C, bias, target, loss, pred_out,
+                          inv_n);
+}
+
+// the loss scalar's zero, as a launch: a graph capture records it as a kernel
+__global__ void head_zero_loss_kernel(float* loss) { *loss = 0.f; }
 
 // 1 when (C, H) is served by the fused kernel
 extern "C" int head_bwd_supported(int C, int H) {
@@ -416,6 +482,33 @@ extern "C" hipError_t launch_head_ce(const bf16raw* w, const float* bias, const 
     default: HEAD_CE_LAUNCH(512); break;
   }
 #undef HEAD_CE_LAUNCH
+  HIP_CHECK_LAUNCH();
+  return hipSuccess;
+}
+
+// Same shape range and grid rule again; target is bf16 [B, C].  loss is
+// defined, not accumulated: a one-thread kernel zeroes it on the stream first.
+extern "C" hipError_t launch_head_mse(const bf16raw* w, const float* bias, const bf16raw* y_in,
+                                      const bf16raw* target, bf16raw* dz_in, float* dw, float* db,
+                                      float* loss, bf16raw* pred_out, int B, int C, int H,
+                                      int max_blocks, int num_cus, hipStream_t stream) {
+  if (!head_bwd_supported(C, H) || B < 1) return hipErrorInvalidValue;
+  const int ntiles = (B + head_rows(H) - 1) / head_rows(H);
+  int grid = 2 * (num_cus > 0 ? num_cus : 256);
+  if (max_blocks > 0 && grid > max_blocks) grid = max_blocks;
+  if (grid > ntiles) grid = ntiles;
+  const float inv_n = 1.0f / ((int64_t)B * C);
+  head_zero_loss_kernel<<<dim3(1), dim3(1), 0, stream>>>(loss);
+#define HEAD_MSE_LAUNCH(HH)                                                   \
+  head_mse_kernel<HH><<<dim3(grid), dim3(HEAD_THREADS), 0, stream>>>(         \
+      w, bias, y_in, target, dz_in, dw, db, loss, pred_out, B, C, inv_n)
+  switch (H) {
+    case 64: HEAD_MSE_LAUNCH(64); break;
+    case 128: HEAD_MSE_LAUNCH(128); break;
+    case 256: HEAD_MSE_LAUNCH(256); break;
+    default: HEAD_MSE_LAUNCH(512); break;
+  }
+#undef HEAD_MSE_LAUNCH
   HIP_CHECK_LAUNCH();
   return hipSuccess;
 }

@@ -12,8 +12,8 @@ Layer stacks (hip_mlp_chain) fold the ReLU mask into the consumer's dgrad
 epilogue, give a big-batch hidden layer on a ReLU output its masked dgrad, dW
 and db from one pass over dz and its input (hidden_bwd.hip), and run a small
 classifier head's whole backward in one pass; a
-train step under cross-entropy (mlp_chain_ce_step) also folds the head's
-forward and the loss into that pass.
+train step under cross-entropy (mlp_chain_ce_step) or mean squared error
+(mlp_chain_mse_step) also folds the head's forward and the loss into that pass.
 
 The CPU fallback keeps identical semantics so the same model code runs in the
 no-GPU sandbox; on a GPU the extension is REQUIRED (ops.ext() raises).
@@ -435,15 +435,41 @@ def linear_head_ce(y_in, w, bias, target, dw, db=None, want_logits: bool = False
     return loss, dz_in, (logits if want_logits else None)
 
 
+# Tests flip this to force forward -> mse_fused -> head backward for the head.
+_HEAD_MSE_FUSION = True
+
+
+def linear_head_mse(y_in, w, bias, target, dw, db=None, want_pred: bool = False,
+                    max_blocks: int = 0):
+    """Training pass of a bias-only head ``y_in @ w^T + bias`` on a ReLU
+    output ``y_in`` under mean squared error against ``target`` (bf16
+    ``[B, C]``), with the loss's upstream gradient fixed at 1.  Returns
+    ``(loss, dz_in, pred)``: the fp32 scalar loss (mean over all ``B * C``
+    elements), ``dz_in = (dpred @ w) * (y_in > 0)`` and the bf16 predictions
+    (``None`` unless ``want_pred``); accumulates ``dw += dpred^T @ y_in`` and
+    ``db += colsum(dpred)`` (fp32, caller zeroes).  One pass over ``y_in``
+    (head_bwd.hip, head_mse_kernel) where the shape qualifies, else
+    linear_fwd -> mse_fused -> linear_head_bwd."""
+    ext = ops.ext()
+    if _HEAD_MSE_FUSION and _head_bwd_ok(ext, w):
+        loss, dz_in, pred = ext.linear_head_mse(y_in, w, bias, target, dw, db, want_pred,
+                                                max_blocks)
+        return loss, dz_in, (pred if want_pred else None)
+    pred = ext.linear_fwd(y_in, w, bias, False, _LINEAR_STREAM)
+    loss, dpred = ext.mse_fused(pred, target)
+    dz_in = linear_head_bwd(dpred, w, y_in, dw, db, max_blocks)
+    return loss, dz_in, (pred if want_pred else None)
+
+
 def _grad_is_direct(p) -> bool:
     return (p.requires_grad and p.grad is not None and p.grad.dtype == torch.float32
             and p.grad.is_contiguous() and getattr(p, "_bucket_notify", None) is not None)
 
 
-def mlp_chain_ce_supported(x: torch.Tensor, layers) -> bool:
-    """Can ``mlp_chain_ce_step`` run this stack: a GPU input that needs no
-    gradient, a plain head the one-pass kernel serves on top of a ReLU layer,
-    and every parameter's gradient going straight into its bucket view."""
+def _mlp_chain_step_supported(x: torch.Tensor, layers) -> bool:
+    """A GPU input that needs no gradient, a plain head the one-pass kernels
+    serve on top of a ReLU layer, and every parameter's gradient going
+    straight into its bucket view."""
     if not (x.is_cuda and not x.requires_grad and len(layers) >= 2):
         return False
     if layers[-1][2] or not layers[-2][2]:
@@ -454,8 +480,30 @@ def mlp_chain_ce_supported(x: torch.Tensor, layers) -> bool:
         if b is not None and not _grad_is_direct(b):
             return False
     w = layers[-1][0]
-    return bool(_HEAD_CE_FUSION and _HEAD_FUSION
-                and ops.ext().head_bwd_supported(w.shape[0], w.shape[1]))
+    return bool(_HEAD_FUSION and ops.ext().head_bwd_supported(w.shape[0], w.shape[1]))
+
+
+def mlp_chain_ce_supported(x: torch.Tensor, layers) -> bool:
+    """Can ``mlp_chain_ce_step`` run this stack (_mlp_chain_step_supported)."""
+    return bool(_HEAD_CE_FUSION and _mlp_chain_step_supported(x, layers))
+
+
+def mlp_chain_mse_supported(x: torch.Tensor, layers, target: torch.Tensor) -> bool:
+    """Can ``mlp_chain_mse_step`` run this stack (_mlp_chain_step_supported)
+    against ``target``: floating point, one value per row and head output."""
+    if not (_HEAD_MSE_FUSION and _mlp_chain_step_supported(x, layers)):
+        return False
+    rows = x.numel() // x.shape[-1]
+    return bool(target.is_floating_point() and target.is_cuda
+                and target.numel() == rows * layers[-1][0].shape[0])
+
+
+def _rows_bf16(x: torch.Tensor) -> torch.Tensor:
+    if x.dtype != torch.bfloat16:
+        x = x.to(torch.bfloat16)
+    if not x.is_contiguous():
+        x = x.contiguous()
+    return x.reshape(-1, x.shape[-1])
 
 
 @torch.no_grad()
@@ -468,21 +516,33 @@ def mlp_chain_ce_step(x: torch.Tensor, layers, target: torch.Tensor) -> torch.Te
     share one pass over the last hidden activation (linear_head_ce).  The
     rest is _MLPChainFn's kernel sequence.  Callers check
     ``mlp_chain_ce_supported`` first."""
-    ext = ops.ext()
-    if x.dtype != torch.bfloat16:
-        x = x.to(torch.bfloat16)
-    if not x.is_contiguous():
-        x = x.contiguous()
-    x = x.reshape(-1, x.shape[-1])
     target = target.flatten().long().contiguous()
+    return _mlp_chain_step(_rows_bf16(x), layers, linear_head_ce, target)
+
+
+@torch.no_grad()
+def mlp_chain_mse_step(x: torch.Tensor, layers, target: torch.Tensor) -> torch.Tensor:
+    """``mlp_chain_ce_step`` for regression: mean squared error against
+    ``target`` (any floating dtype, ``rows * outputs`` elements; rounded to
+    bf16 as hip_mse rounds it), the head through linear_head_mse.  Callers
+    check ``mlp_chain_mse_supported`` first."""
+    x = _rows_bf16(x)
+    target = target.to(torch.bfloat16).contiguous().view(x.shape[0], layers[-1][0].shape[0])
+    return _mlp_chain_step(x, layers, linear_head_mse, target)
+
+
+def _mlp_chain_step(x, layers, head, target) -> torch.Tensor:
+    """The layer walk of the explicit train steps: ``head`` is linear_head_ce
+    or linear_head_mse, ``x`` bf16 rows."""
+    ext = ops.ext()
     n = len(layers)
     acts, wbs = [x], []
     for w, b, relu in layers[:-1]:
         wbs.append(ext.cast_f32_bf16(w))
         acts.append(ext.linear_fwd(acts[-1], wbs[-1], b, bool(relu), _LINEAR_STREAM))
     w, b, _ = layers[-1]
-    loss, dz, _ = linear_head_ce(acts[-1], ext.cast_f32_bf16(w), b, target, w.grad,
-                                 b.grad if b is not None else None)
+    loss, dz, _ = head(acts[-1], ext.cast_f32_bf16(w), b, target, w.grad,
+                       b.grad if b is not None else None)
     w._bucket_notify()
     if b is not None:
         b._bucket_notify()

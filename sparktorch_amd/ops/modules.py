@@ -33,6 +33,8 @@ from sparktorch_amd.ops.functional import (
     hip_mlp_predict,
     mlp_chain_ce_step,
     mlp_chain_ce_supported,
+    mlp_chain_mse_step,
+    mlp_chain_mse_supported,
     hip_relu,
     hip_mse,
 )
@@ -359,6 +361,15 @@ class MnistMLPFused(nn.Module):
         (mlp_chain_ce_step): returns the loss, gradients land in the bucket
         views.  Only where ``ce_step_supported(x)``."""
         return mlp_chain_ce_step(x, self._layers(), target)
+
+    def mse_step_supported(self, x: torch.Tensor, y: torch.Tensor) -> bool:
+        return mlp_chain_mse_supported(x, self._layers(), y)
+
+    def mse_step(self, x: torch.Tensor, y: torch.Tensor) -> torch.Tensor:
+        """Forward + mean squared error + backward without autograd
+        (mlp_chain_mse_step): returns the loss, gradients land in the bucket
+        views.  Only where ``mse_step_supported(x, y)``."""
+        return mlp_chain_mse_step(x, self._layers(), y)
 
 
 def convert_model_for_mi355x(model: nn.Module) -> nn.Module:

@@ -159,6 +159,18 @@ class SyncTrainer:
             and self.model.ce_step_supported(x)
         ):
             return self.model.ce_step(x, y)
+        # The same for regression: the fused mean squared error and a model
+        # with MnistMLPFused.mse_step.  Autoencoder mode (y is None) has no
+        # target tensor to hand over and keeps the autograd route.
+        if (
+            self.native
+            and type(self.criterion).__name__ == "HipMSE"
+            and (not self.compile_mode or self.compile_mode == "hipgraph")
+            and y is not None
+            and hasattr(self.model, "mse_step_supported")
+            and self.model.mse_step_supported(x, y)
+        ):
+            return self.model.mse_step(x, y)
         pred = self.model(x)
         loss = compute_loss(self.criterion, pred, y)
         loss.backward()
