@@ -20,12 +20,14 @@ OPS_DIR = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(OPS_DIR, "csrc")
 BUILD_DIR = os.path.join(OPS_DIR, "build")
 
-HIP_SOURCES = ["elementwise.hip", "loss.hip", "gemm.hip", "conv.hip", "norm.hip", "conv_nhwc.hip", "conv_implicit.hip", "head_bwd.hip", "linear_wgrad.hip", "sample_gather.hip", "linear_stream.hip", "mlp_predict.hip", "hidden_bwd.hip"]
+HIP_SOURCES = ["elementwise.hip", "loss.hip", "gemm.hip", "conv.hip", "norm.hip", "conv_nhwc.hip", "conv_implicit.hip", "head_bwd.hip", "linear_wgrad.hip", "sample_gather.hip", "linear_stream.hip", "mlp_predict.hip", "hidden_bwd.hip", "linear_mse.hip"]
 CPP_SOURCES = ["bindings.cpp"]
-# Extra hipcc flags per translation unit.  hidden_bwd.hip is compiled without
-# packed fp32 instructions (v_pk_*_f32).
+# Extra hipcc flags per translation unit.  hidden_bwd.hip and linear_mse.hip
+# are compiled without packed fp32 instructions (v_pk_*_f32).
+_NO_PK_F32 = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
 HIP_EXTRA_FLAGS = {
-    "hidden_bwd.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"],
+    "hidden_bwd.hip": _NO_PK_F32,
+    "linear_mse.hip": _NO_PK_F32,
 }
 
 ROCM = os.environ.get("ROCM_PATH", "/opt/rocm")

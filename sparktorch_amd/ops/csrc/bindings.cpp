@@ -69,6 +69,11 @@ hipError_t launch_head_ce(const bf16raw*, const float*, const bf16raw*, const in
                           float*, float*, float*, bf16raw*, int, int, int, int, int, hipStream_t);
 hipError_t launch_head_mse(const bf16raw*, const float*, const bf16raw*, const bf16raw*, bf16raw*,
                            float*, float*, float*, bf16raw*, int, int, int, int, int, hipStream_t);
+int linear_mse_supported(int, int);
+int linear_mse_chunk_cols(int);
+int64_t linear_mse_min_rows();
+hipError_t launch_linear_mse(const bf16raw*, const bf16raw*, const float*, const bf16raw*, bf16raw*,
+                             bf16raw*, float*, int, int, int, int, int, hipStream_t);
 int mlp_predict_supported(int, const int*, int, int, int64_t);
 int64_t mlp_predict_min_rows();
 hipError_t launch_mlp_predict(const bf16raw*, const bf16raw* const*, const float* const*,
@@ -695,6 +700,45 @@ std::tuple<at::Tensor, at::Tensor, at::Tensor> linear_head_mse(
                             want_pred ? (bf16raw*)pred.data_ptr() : nullptr, (int)B, (int)C,
                             (int)H, (int)max_blocks, head_num_cus(), cur_stream()));
   return {loss, dz_in, pred};
+}
+
+// Forward of a wide output layer and its mean squared error in one pass over
+// the layer's input (linear_mse.hip): returns (loss, dpred, pred or an empty
+// tensor) against a bf16 [B, N] target; the loss is defined by the call.
+bool linear_mse_ok(int64_t N, int64_t H) { return linear_mse_supported((int)N, (int)H) != 0; }
+
+int64_t linear_mse_chunk_cols_py(int64_t H) { return linear_mse_chunk_cols((int)H); }
+
+std::tuple<at::Tensor, at::Tensor, at::Tensor> linear_mse(
+    at::Tensor y_in, at::Tensor w, c10::optional<at::Tensor> bias, at::Tensor target,
+    bool want_pred, int64_t max_blocks) {
+  check_gpu_contig(y_in, at::kBFloat16, "y_in");
+  check_gpu_contig(w, at::kBFloat16, "w");
+  check_gpu_contig(target, at::kBFloat16, "target");
+  TORCH_CHECK(y_in.dim() == 2 && w.dim() == 2 && target.dim() == 2);
+  int64_t B = y_in.size(0), H = y_in.size(1), N = w.size(0);
+  TORCH_CHECK(B >= 1 && B < (1LL << 31) && w.size(1) == H && target.size(0) == B &&
+                  target.size(1) == N,
+              "shape mismatch");
+  TORCH_CHECK(linear_mse_ok(N, H), "linear_mse: unsupported (N, H); use the two-step route");
+  const float* bp = nullptr;
+  if (bias.has_value()) {
+    check_gpu_contig(*bias, at::kFloat, "bias");
+    TORCH_CHECK(bias->numel() == N);
+    bp = bias->data_ptr<float>();
+  }
+  auto loss = at::empty({}, y_in.options().dtype(at::kFloat));
+  auto dpred = at::empty({B, N}, y_in.options());
+  auto pred = want_pred ? at::empty({B, N}, y_in.options()) : at::empty({0}, y_in.options());
+  TORCH_CHECK(aligned16(y_in) && aligned16(w) && aligned16(target) && aligned16(dpred) &&
+                  (!want_pred || aligned16(pred)) && (((uintptr_t)bp) & 15) == 0,
+              "linear_mse wants 16-byte aligned operands");
+  CHECK_HIP(launch_linear_mse((const bf16raw*)y_in.data_ptr(), (const bf16raw*)w.data_ptr(), bp,
+                              (const bf16raw*)target.data_ptr(), (bf16raw*)dpred.data_ptr(),
+                              want_pred ? (bf16raw*)pred.data_ptr() : nullptr,
+                              loss.data_ptr<float>(), (int)B, (int)N, (int)H, (int)max_blocks,
+                              head_num_cus(), cur_stream()));
+  return {loss, dpred, pred};
 }
 
 // Whole-MLP inference in one launch (mlp_predict.hip): x through the hidden
@@ -1463,6 +1507,16 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "head forward + mean squared error + one-pass head backward: (loss, dz_in, pred)",
         py::arg("y_in"), py::arg("w"), py::arg("bias"), py::arg("target"), py::arg("dw"),
         py::arg("db"), py::arg("want_pred") = false, py::arg("max_blocks") = 0);
+  m.def("linear_mse_supported", &linear_mse_ok,
+        "does the one-pass wide-layer forward + MSE kernel serve (N, H)");
+  m.def("linear_mse_chunk_cols", &linear_mse_chunk_cols_py,
+        "W columns the one-pass forward + MSE kernel stages at a time at width H");
+  m.def("linear_mse_min_rows", &linear_mse_min_rows,
+        "rows from which functional.linear_mse takes the one-pass kernel (measured)");
+  m.def("linear_mse", &linear_mse,
+        "wide layer forward + mean squared error in one pass: (loss, dpred, pred)",
+        py::arg("y_in"), py::arg("w"), py::arg("bias"), py::arg("target"),
+        py::arg("want_pred") = false, py::arg("max_blocks") = 0);
   m.def("mlp_predict_supported", &mlp_predict_ok,
         "does the one-launch MLP inference kernel serve (K0, hidden widths, C)");
   m.def("mlp_predict_min_rows", &mlp_predict_min_rows_py,

@@ -13,7 +13,9 @@ epilogue, give a big-batch hidden layer on a ReLU output its masked dgrad, dW
 and db from one pass over dz and its input (hidden_bwd.hip), and run a small
 classifier head's whole backward in one pass; a
 train step under cross-entropy (mlp_chain_ce_step) or mean squared error
-(mlp_chain_mse_step) also folds the head's forward and the loss into that pass.
+(mlp_chain_mse_step) also folds the head's forward and the loss into that pass;
+a wide output layer under mean squared error (an autoencoder's) gets its
+forward and the loss from one pass (linear_mse).
 
 The CPU fallback keeps identical semantics so the same model code runs in the
 no-GPU sandbox; on a GPU the extension is REQUIRED (ops.ext() raises).
@@ -461,15 +463,62 @@ def linear_head_mse(y_in, w, bias, target, dw, db=None, want_pred: bool = False,
     return loss, dz_in, (pred if want_pred else None)
 
 
+# Tests flip this to force linear_fwd -> mse_fused for a wide output layer.
+_LINEAR_MSE_FUSION = True
+# None: the kernel's measured row threshold.  Tests lower it to drive small
+# batches through the kernel.
+_LINEAR_MSE_MIN_ROWS = None
+
+
+def linear_mse_min_rows() -> int:
+    """Rows from which ``linear_mse`` takes the one-pass kernel (measured:
+    profiles/linear_mse.md)."""
+    if _LINEAR_MSE_MIN_ROWS is not None:
+        return int(_LINEAR_MSE_MIN_ROWS)
+    return int(ops.ext().linear_mse_min_rows())
+
+
+def _linear_mse_ok(ext, y_in, w, bias, target) -> bool:
+    """Does the one-pass kernel (linear_mse.hip) replace linear_fwd ->
+    mse_fused: the flag on, a bf16 weight of a served (N, H), enough rows,
+    16-byte aligned operands."""
+    if not (_LINEAR_MSE_FUSION and w.dtype == torch.bfloat16
+            and ext.linear_mse_supported(w.shape[0], w.shape[1])
+            and y_in.shape[0] >= linear_mse_min_rows()):
+        return False
+    ops_ = [y_in, w, target] + ([bias] if bias is not None else [])
+    return all(t.data_ptr() % 16 == 0 for t in ops_)
+
+
+def linear_mse(y_in, w, bias, target, want_pred: bool = False, max_blocks: int = 0):
+    """Forward of a bias-only (no activation) layer ``y_in @ w^T + bias`` and
+    its mean squared error against ``target`` (bf16 ``[B, N]``), with the
+    loss's upstream gradient fixed at 1.  Returns ``(loss, dpred, pred)``: the
+    fp32 scalar loss (mean over all ``B * N`` elements), ``dpred = 2 (pred -
+    target) / (B N)`` in bf16 and the bf16 predictions (``None`` unless
+    ``want_pred``).  One pass over ``y_in`` and ``target`` (linear_mse.hip)
+    for H in {64, 128, 256} inputs, N >= 32, N % 16 == 0 outputs and at least
+    ``linear_mse_min_rows()`` rows, else linear_fwd -> mse_fused; the results are bit-identical but for the
+    summation order of the loss."""
+    ext = ops.ext()
+    if _linear_mse_ok(ext, y_in, w, bias, target):
+        loss, dpred, pred = ext.linear_mse(y_in, w, bias, target, want_pred, max_blocks)
+        return loss, dpred, (pred if want_pred else None)
+    pred = ext.linear_fwd(y_in, w, bias, False, _LINEAR_STREAM)
+    loss, dpred = ext.mse_fused(pred, target)
+    return loss, dpred, (pred if want_pred else None)
+
+
 def _grad_is_direct(p) -> bool:
     return (p.requires_grad and p.grad is not None and p.grad.dtype == torch.float32
             and p.grad.is_contiguous() and getattr(p, "_bucket_notify", None) is not None)
 
 
-def _mlp_chain_step_supported(x: torch.Tensor, layers) -> bool:
+def _mlp_chain_step_supported(x: torch.Tensor, layers, wide_head: bool = False) -> bool:
     """A GPU input that needs no gradient, a plain head the one-pass kernels
     serve on top of a ReLU layer, and every parameter's gradient going
-    straight into its bucket view."""
+    straight into its bucket view.  ``wide_head``: a head that
+    head_bwd_supported rejects and linear_mse serves counts too."""
     if not (x.is_cuda and not x.requires_grad and len(layers) >= 2):
         return False
     if layers[-1][2] or not layers[-2][2]:
@@ -480,7 +529,16 @@ def _mlp_chain_step_supported(x: torch.Tensor, layers) -> bool:
         if b is not None and not _grad_is_direct(b):
             return False
     w = layers[-1][0]
-    return bool(_HEAD_FUSION and ops.ext().head_bwd_supported(w.shape[0], w.shape[1]))
+    ext = ops.ext()
+    if _HEAD_FUSION and ext.head_bwd_supported(w.shape[0], w.shape[1]):
+        return True
+    return bool(wide_head and _wide_head(ext, w))
+
+
+def _wide_head(ext, w) -> bool:
+    """A last layer for linear_mse: too wide for the one-pass head kernels."""
+    return bool(_LINEAR_MSE_FUSION and not ext.head_bwd_supported(w.shape[0], w.shape[1])
+                and ext.linear_mse_supported(w.shape[0], w.shape[1]))
 
 
 def mlp_chain_ce_supported(x: torch.Tensor, layers) -> bool:
@@ -489,9 +547,12 @@ def mlp_chain_ce_supported(x: torch.Tensor, layers) -> bool:
 
 
 def mlp_chain_mse_supported(x: torch.Tensor, layers, target: torch.Tensor) -> bool:
-    """Can ``mlp_chain_mse_step`` run this stack (_mlp_chain_step_supported)
+    """Can ``mlp_chain_mse_step`` run this stack (_mlp_chain_step_supported,
+    with a narrow head for linear_head_mse or a wide one for linear_mse)
     against ``target``: floating point, one value per row and head output."""
-    if not (_HEAD_MSE_FUSION and _mlp_chain_step_supported(x, layers)):
+    if not _mlp_chain_step_supported(x, layers, wide_head=True):
+        return False
+    if not (_HEAD_MSE_FUSION or _wide_head(ops.ext(), layers[-1][0])):
         return False
     rows = x.numel() // x.shape[-1]
     return bool(target.is_floating_point() and target.is_cuda
@@ -524,16 +585,22 @@ def mlp_chain_ce_step(x: torch.Tensor, layers, target: torch.Tensor) -> torch.Te
 def mlp_chain_mse_step(x: torch.Tensor, layers, target: torch.Tensor) -> torch.Tensor:
     """``mlp_chain_ce_step`` for regression: mean squared error against
     ``target`` (any floating dtype, ``rows * outputs`` elements; rounded to
-    bf16 as hip_mse rounds it), the head through linear_head_mse.  Callers
-    check ``mlp_chain_mse_supported`` first."""
+    bf16 as hip_mse rounds it), the head through linear_head_mse.  A wide
+    head (an autoencoder's output layer: _wide_head) takes its forward and
+    the loss from linear_mse and its backward from the layer walk, as a
+    hidden layer.  Callers check ``mlp_chain_mse_supported`` first."""
     x = _rows_bf16(x)
-    target = target.to(torch.bfloat16).contiguous().view(x.shape[0], layers[-1][0].shape[0])
-    return _mlp_chain_step(x, layers, linear_head_mse, target)
+    w = layers[-1][0]
+    target = target.to(torch.bfloat16).contiguous().view(x.shape[0], w.shape[0])
+    head = None if _wide_head(ops.ext(), w) else linear_head_mse
+    return _mlp_chain_step(x, layers, head, target)
 
 
 def _mlp_chain_step(x, layers, head, target) -> torch.Tensor:
     """The layer walk of the explicit train steps: ``head`` is linear_head_ce
-    or linear_head_mse, ``x`` bf16 rows."""
+    or linear_head_mse, or None for a wide head under mean squared error
+    (linear_mse gives the loss and the head's dz; the walk then starts at the
+    head); ``x`` bf16 rows."""
     ext = ops.ext()
     n = len(layers)
     acts, wbs = [x], []
@@ -541,12 +608,18 @@ def _mlp_chain_step(x, layers, head, target) -> torch.Tensor:
         wbs.append(ext.cast_f32_bf16(w))
         acts.append(ext.linear_fwd(acts[-1], wbs[-1], b, bool(relu), _LINEAR_STREAM))
     w, b, _ = layers[-1]
-    loss, dz, _ = head(acts[-1], ext.cast_f32_bf16(w), b, target, w.grad,
-                       b.grad if b is not None else None)
-    w._bucket_notify()
-    if b is not None:
-        b._bucket_notify()
-    for i in range(n - 2, -1, -1):
+    wbs.append(ext.cast_f32_bf16(w))
+    if head is None:
+        loss, dz, _ = linear_mse(acts[-1], wbs[-1], b, target)
+        first = n - 1
+    else:
+        loss, dz, _ = head(acts[-1], wbs[-1], b, target, w.grad,
+                           b.grad if b is not None else None)
+        w._bucket_notify()
+        if b is not None:
+            b._bucket_notify()
+        first = n - 2
+    for i in range(first, -1, -1):
         w, b, _ = layers[i]
         if i > 0 and layers[i - 1][2] and _hidden_bwd_ok(ext, dz, acts[i], wbs[i]):
             dz, _, _ = _hidden_bwd(ext, dz, acts[i], w, wbs[i], b, b is not None)

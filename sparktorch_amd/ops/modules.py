@@ -372,6 +372,39 @@ class MnistMLPFused(nn.Module):
         return mlp_chain_mse_step(x, self._layers(), y)
 
 
+class MLPAutoEncoderFused(nn.Module):
+    """in_dim-256-64-256-in_dim autoencoder MLP (any ``widths``): ReLU after
+    every layer but the last, whose width is ``in_dim``.  Layers are named
+    ``fc1 .. fcK``; a plain torch module with the same names loads its
+    state_dict.  Under mean squared error against its own input the train
+    step takes the output layer's forward and the loss from one pass
+    (mlp_chain_mse_step, linear_mse)."""
+
+    def __init__(self, in_dim: int = 784, widths=(256, 64, 256)):
+        super().__init__()
+        dims = [in_dim] + [int(w) for w in widths] + [in_dim]
+        self.depth = len(dims) - 1
+        for i in range(self.depth):
+            act = "relu" if i < self.depth - 1 else None
+            setattr(self, "fc%d" % (i + 1), HipLinear(dims[i], dims[i + 1], activation=act))
+
+    def _layers(self):
+        fcs = [getattr(self, "fc%d" % (i + 1)) for i in range(self.depth)]
+        return [(fc.weight, fc.bias, fc.activation == "relu") for fc in fcs]
+
+    def forward(self, x: torch.Tensor) -> torch.Tensor:
+        return hip_mlp_chain(x, self._layers())
+
+    def mse_step_supported(self, x: torch.Tensor, y: torch.Tensor) -> bool:
+        return mlp_chain_mse_supported(x, self._layers(), y)
+
+    def mse_step(self, x: torch.Tensor, y: torch.Tensor) -> torch.Tensor:
+        """Forward + mean squared error + backward without autograd
+        (mlp_chain_mse_step): returns the loss, gradients land in the bucket
+        views.  Only where ``mse_step_supported(x, y)``."""
+        return mlp_chain_mse_step(x, self._layers(), y)
+
+
 def convert_model_for_mi355x(model: nn.Module) -> nn.Module:
     """Swap torch modules for their native-kernel equivalents in place
     (adopting the SAME Parameter objects, so optimizers/buckets are

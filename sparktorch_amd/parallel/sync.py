@@ -160,8 +160,10 @@ class SyncTrainer:
         ):
             return self.model.ce_step(x, y)
         # The same for regression: the fused mean squared error and a model
-        # with MnistMLPFused.mse_step.  Autoencoder mode (y is None) has no
-        # target tensor to hand over and keeps the autograd route.
+        # with MnistMLPFused.mse_step, or MLPAutoEncoderFused.mse_step with
+        # the input as its own target (handle_model and the device sampler
+        # hand y = x down in autoencoder mode).  A bare train_step(x, None)
+        # has no target tensor to hand over and keeps the autograd route.
         if (
             self.native
             and type(self.criterion).__name__ == "HipMSE"
