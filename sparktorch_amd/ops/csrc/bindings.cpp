@@ -69,6 +69,11 @@ hipError_t launch_head_ce(const bf16raw*, const float*, const bf16raw*, const in
                           float*, float*, float*, bf16raw*, int, int, int, int, int, hipStream_t);
 hipError_t launch_head_mse(const bf16raw*, const float*, const bf16raw*, const bf16raw*, bf16raw*,
                            float*, float*, float*, bf16raw*, int, int, int, int, int, hipStream_t);
+int hidden_head_ce_supported(int, int, int);
+int64_t hidden_head_ce_min_rows();
+hipError_t launch_hidden_head_ce(const bf16raw*, const bf16raw*, const float*, const bf16raw*,
+                                 const float*, const int64_t*, bf16raw*, float*, float*, float*,
+                                 bf16raw*, bf16raw*, int, int, int, int, int, int, hipStream_t);
 int linear_mse_supported(int, int);
 int linear_mse_chunk_cols(int);
 int64_t linear_mse_min_rows();
@@ -700,6 +705,67 @@ std::tuple<at::Tensor, at::Tensor, at::Tensor> linear_head_mse(
                             want_pred ? (bf16raw*)pred.data_ptr() : nullptr, (int)B, (int)C,
                             (int)H, (int)max_blocks, head_num_cus(), cur_stream()));
   return {loss, dz_in, pred};
+}
+
+// The last hidden layer's forward fused into the head's loss pass
+// (hidden_head_ce.hip): what linear_fwd(x, w2, b2, relu) followed by
+// linear_head_ce(h2, w3, b3, target, dw3, db3) compute, without h2 going
+// through memory.  Returns (loss, dz2, logits or an empty tensor, h2 or an
+// empty tensor); dw3 / db3 are accumulated into, the loss is defined.
+bool hidden_head_ce_ok(int64_t K_in, int64_t H, int64_t C) {
+  return K_in < (1LL << 31) && H < (1LL << 31) && C < (1LL << 31) &&
+         hidden_head_ce_supported((int)K_in, (int)H, (int)C) != 0;
+}
+
+std::tuple<at::Tensor, at::Tensor, at::Tensor, at::Tensor> linear_hidden_head_ce(
+    at::Tensor x, at::Tensor w2, c10::optional<at::Tensor> b2, at::Tensor w3,
+    c10::optional<at::Tensor> b3, at::Tensor target, at::Tensor dw3,
+    c10::optional<at::Tensor> db3, bool want_logits, bool want_h2, int64_t max_blocks) {
+  check_gpu_contig(x, at::kBFloat16, "x");
+  check_gpu_contig(w2, at::kBFloat16, "w2");
+  check_gpu_contig(w3, at::kBFloat16, "w3");
+  check_gpu_contig(target, at::kLong, "target");
+  check_gpu_contig(dw3, at::kFloat, "dw3");
+  TORCH_CHECK(x.dim() == 2 && w2.dim() == 2 && w3.dim() == 2 && target.dim() == 1);
+  int64_t B = x.size(0), K = x.size(1), H = w2.size(0), C = w3.size(0);
+  TORCH_CHECK(B >= 1 && B < (1LL << 31) - 128 && w2.size(1) == K && w3.size(1) == H &&
+                  target.size(0) == B && dw3.dim() == 2 && dw3.size(0) == C && dw3.size(1) == H,
+              "shape mismatch");
+  TORCH_CHECK(hidden_head_ce_ok(K, H, C),
+              "linear_hidden_head_ce: unsupported (K_in, H, C); use linear_fwd + linear_head_ce");
+  const float *b2p = nullptr, *b3p = nullptr;
+  if (b2.has_value()) {
+    check_gpu_contig(*b2, at::kFloat, "b2");
+    TORCH_CHECK(b2->numel() == H);
+    b2p = b2->data_ptr<float>();
+  }
+  if (b3.has_value()) {
+    check_gpu_contig(*b3, at::kFloat, "b3");
+    TORCH_CHECK(b3->numel() == C);
+    b3p = b3->data_ptr<float>();
+  }
+  float* dbp = nullptr;
+  if (db3.has_value()) {
+    check_gpu_contig(*db3, at::kFloat, "db3");
+    TORCH_CHECK(db3->numel() == C);
+    dbp = db3->data_ptr<float>();
+  }
+  auto loss = at::empty({}, x.options().dtype(at::kFloat));
+  auto dz = at::empty({B, H}, x.options());
+  auto logits = want_logits ? at::empty({B, C}, x.options()) : at::empty({0}, x.options());
+  auto h2 = want_h2 ? at::empty({B, H}, x.options()) : at::empty({0}, x.options());
+  TORCH_CHECK(((uintptr_t)x.data_ptr() & 15) == 0 && ((uintptr_t)w2.data_ptr() & 15) == 0 &&
+                  ((uintptr_t)w3.data_ptr() & 15) == 0 && ((uintptr_t)dz.data_ptr() & 15) == 0 &&
+                  (!want_h2 || ((uintptr_t)h2.data_ptr() & 15) == 0),
+              "linear_hidden_head_ce wants 16-byte aligned activations and weights");
+  CHECK_HIP(launch_hidden_head_ce(
+      (const bf16raw*)x.data_ptr(), (const bf16raw*)w2.data_ptr(), b2p,
+      (const bf16raw*)w3.data_ptr(), b3p, target.data_ptr<int64_t>(), (bf16raw*)dz.data_ptr(),
+      dw3.data_ptr<float>(), dbp, loss.data_ptr<float>(),
+      want_logits ? (bf16raw*)logits.data_ptr() : nullptr,
+      want_h2 ? (bf16raw*)h2.data_ptr() : nullptr, (int)B, (int)K, (int)H, (int)C,
+      (int)max_blocks, head_num_cus(), cur_stream()));
+  return {loss, dz, logits, h2};
 }
 
 // Forward of a wide output layer and its mean squared error in one pass over
@@ -1507,6 +1573,16 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "head forward + mean squared error + one-pass head backward: (loss, dz_in, pred)",
         py::arg("y_in"), py::arg("w"), py::arg("bias"), py::arg("target"), py::arg("dw"),
         py::arg("db"), py::arg("want_pred") = false, py::arg("max_blocks") = 0);
+  m.def("hidden_head_ce_supported", &hidden_head_ce_ok,
+        "does the fused hidden-layer forward + head loss pass serve (K_in, H, C)");
+  m.def("hidden_head_ce_min_rows", &hidden_head_ce_min_rows,
+        "rows from which functional._mlp_chain_step takes that kernel (measured)");
+  m.def("linear_hidden_head_ce", &linear_hidden_head_ce,
+        "relu hidden layer forward + head forward + cross-entropy + head backward in one pass: "
+        "(loss, dz2, logits, h2)",
+        py::arg("x"), py::arg("w2"), py::arg("b2"), py::arg("w3"), py::arg("b3"),
+        py::arg("target"), py::arg("dw3"), py::arg("db3"), py::arg("want_logits") = false,
+        py::arg("want_h2") = false, py::arg("max_blocks") = 0);
   m.def("linear_mse_supported", &linear_mse_ok,
         "does the one-pass wide-layer forward + MSE kernel serve (N, H)");
   m.def("linear_mse_chunk_cols", &linear_mse_chunk_cols_py,

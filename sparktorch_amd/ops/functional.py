@@ -437,6 +437,61 @@ def linear_head_ce(y_in, w, bias, target, dw, db=None, want_logits: bool = False
     return loss, dz_in, (logits if want_logits else None)
 
 
+# Tests flip this to force linear_fwd -> linear_head_ce for the last hidden
+# layer and the head.
+_HIDDEN_HEAD_CE_FUSION = True
+# None: the kernel's measured row threshold.  Tests lower it to drive small
+# batches through the kernel.
+_HIDDEN_HEAD_CE_MIN_ROWS = None
+
+
+def hidden_head_ce_min_rows() -> int:
+    """Rows from which ``_mlp_chain_step`` fuses the last hidden layer's
+    forward into the head's loss pass (measured: profiles/hidden_head_ce.md)."""
+    if _HIDDEN_HEAD_CE_MIN_ROWS is not None:
+        return int(_HIDDEN_HEAD_CE_MIN_ROWS)
+    return int(ops.ext().hidden_head_ce_min_rows())
+
+
+def _hidden_head_ce_ok(ext, x, w2, b2, w3, b3) -> bool:
+    """Does the fused kernel (hidden_head_ce.hip) replace linear_fwd ->
+    linear_head_ce: both flags on, weights of a served (K_in, H, C), enough
+    rows, 16-byte aligned activations and bf16 weights."""
+    if not (_HIDDEN_HEAD_CE_FUSION and _HEAD_CE_FUSION and w2.dtype == torch.bfloat16
+            and x.dim() == 2 and w2.dim() == 2 and w3.dim() == 2
+            and ext.hidden_head_ce_supported(w2.shape[1], w2.shape[0], w3.shape[0])
+            and x.shape[0] >= hidden_head_ce_min_rows()):
+        return False
+    # the kernel reads the biases float by float; w3 may be the fp32 parameter
+    # standing in for a bf16 cast that does not exist yet (fresh: aligned)
+    ops_ = [x, w2] + ([w3] if w3.dtype == torch.bfloat16 else [])
+    return all(t.data_ptr() % 16 == 0 for t in ops_)
+
+
+def linear_hidden_head_ce(x, w2, b2, w3, b3, target, dw3, db3=None, want_logits: bool = False,
+                          want_h2: bool = False, max_blocks: int = 0):
+    """Training pass of a ReLU hidden layer ``h2 = relu(x @ w2^T + b2)`` and a
+    bias-only head ``h2 @ w3^T + b3`` under mean cross-entropy against
+    ``target`` (int64), with the loss's upstream gradient fixed at 1: what
+    ``linear_fwd(x, w2, b2, relu=True)`` followed by ``linear_head_ce``
+    compute.  Returns ``(loss, dz2, logits, h2)``: the fp32 scalar loss,
+    ``dz2 = (dlogits @ w3) * (h2 > 0)``, and the bf16 logits and hidden
+    activation (``None`` unless asked for); accumulates ``dw3`` and ``db3``
+    (fp32, caller zeroes).  One pass that keeps h2 on chip
+    (hidden_head_ce.hip) for K_in <= 256 (a multiple of 32), H in {128, 256},
+    at most 16 classes and at least ``hidden_head_ce_min_rows()`` rows, else
+    the two calls.  h2, the logits and dz2 are bit-identical on both routes;
+    the loss, dw3 and db3 differ by the order of fp32 sums only."""
+    ext = ops.ext()
+    if _hidden_head_ce_ok(ext, x, w2, b2, w3, b3):
+        loss, dz2, logits, h2 = ext.linear_hidden_head_ce(
+            x, w2, b2, w3, b3, target, dw3, db3, want_logits, want_h2, max_blocks)
+        return loss, dz2, (logits if want_logits else None), (h2 if want_h2 else None)
+    h2 = ext.linear_fwd(x, w2, b2, True, _LINEAR_STREAM)
+    loss, dz2, logits = linear_head_ce(h2, w3, b3, target, dw3, db3, want_logits, max_blocks)
+    return loss, dz2, logits, (h2 if want_h2 else None)
+
+
 # Tests flip this to force forward -> mse_fused -> head backward for the head.
 _HEAD_MSE_FUSION = True
 
@@ -604,17 +659,32 @@ def _mlp_chain_step(x, layers, head, target) -> torch.Tensor:
     ext = ops.ext()
     n = len(layers)
     acts, wbs = [x], []
-    for w, b, relu in layers[:-1]:
+    for w, b, relu in layers[:-2]:
         wbs.append(ext.cast_f32_bf16(w))
         acts.append(ext.linear_fwd(acts[-1], wbs[-1], b, bool(relu), _LINEAR_STREAM))
+    w2, b2, relu2 = layers[-2]
     w, b, _ = layers[-1]
+    wbs.append(ext.cast_f32_bf16(w2))
+    # the last hidden layer's forward goes into the head's loss pass where
+    # hidden_head_ce.hip serves the pair (w stands in for its bf16 cast: the
+    # check reads its shape, and a fresh cast is aligned)
+    fused = (head is linear_head_ce and bool(relu2)
+             and _hidden_head_ce_ok(ext, acts[-1], wbs[-1], b2, w, b))
+    if not fused:
+        acts.append(ext.linear_fwd(acts[-1], wbs[-1], b2, bool(relu2), _LINEAR_STREAM))
     wbs.append(ext.cast_f32_bf16(w))
-    if head is None:
+    if fused:
+        # h2 never exists: acts ends at the hidden layer's input, which is all
+        # the walk from n - 2 down reads
+        loss, dz, _, _ = linear_hidden_head_ce(acts[-1], wbs[-2], b2, wbs[-1], b, target, w.grad,
+                                               b.grad if b is not None else None)
+    elif head is None:
         loss, dz, _ = linear_mse(acts[-1], wbs[-1], b, target)
-        first = n - 1
     else:
         loss, dz, _ = head(acts[-1], wbs[-1], b, target, w.grad,
                            b.grad if b is not None else None)
+    first = n - 1
+    if head is not None:
         w._bucket_notify()
         if b is not None:
             b._bucket_notify()
