@@ -50,6 +50,10 @@ int linear_wgrad_stream_supported(int, int, int64_t);
 int linear_wgrad_stream_can_run(int, int, int64_t);
 hipError_t launch_linear_wgrad_stream(const bf16raw*, const bf16raw*, float*, float*, int64_t, int,
                                       int, int, int, hipStream_t);
+int linear_wgrad_wide_supported(int, int, int64_t);
+int linear_wgrad_wide_can_run(int, int, int64_t);
+hipError_t launch_linear_wgrad_wide(const bf16raw*, const bf16raw*, float*, float*, int64_t, int,
+                                    int, int, int, hipStream_t);
 int hidden_bwd_supported(int, int, int64_t);
 int hidden_bwd_can_run(int, int, int64_t);
 hipError_t launch_hidden_bwd(const bf16raw*, const bf16raw*, const bf16raw*, bf16raw*, float*,
@@ -985,6 +989,40 @@ void linear_wgrad_stream(at::Tensor dz, at::Tensor x, at::Tensor dw, c10::option
                                        (int)max_blocks, head_num_cus(), cur_stream()));
 }
 
+// The same contract for a wide layer on a 64/128/256-wide input
+// (linear_wgrad_wide.hip), which linear_wgrad_stream cannot hold:
+// linear_wgrad_wide_ok is the routing rule (No > 256 and the measured batch
+// threshold); the launcher serves every shape linear_wgrad_wide_runs accepts.
+bool linear_wgrad_wide_runs(int64_t No, int64_t Ki, int64_t B) {
+  return No < (1 << 24) && Ki <= 256 && linear_wgrad_wide_can_run((int)No, (int)Ki, B) != 0;
+}
+bool linear_wgrad_wide_ok(int64_t No, int64_t Ki, int64_t B) {
+  return No < (1 << 24) && Ki <= 256 && linear_wgrad_wide_supported((int)No, (int)Ki, B) != 0;
+}
+
+void linear_wgrad_wide(at::Tensor dz, at::Tensor x, at::Tensor dw, c10::optional<at::Tensor> db,
+                       int64_t max_blocks) {
+  check_gpu_contig(dz, at::kBFloat16, "dz");
+  check_gpu_contig(x, at::kBFloat16, "x");
+  check_gpu_contig(dw, at::kFloat, "dw");
+  TORCH_CHECK(dz.dim() == 2 && x.dim() == 2);
+  int64_t B = dz.size(0), N = dz.size(1), K = x.size(1);
+  TORCH_CHECK(x.size(0) == B && dw.size(0) == N && dw.size(1) == K, "shape mismatch");
+  float* dbp = nullptr;
+  if (db.has_value()) {
+    check_gpu_contig(*db, at::kFloat, "db");
+    TORCH_CHECK(db->numel() == N);
+    dbp = db->data_ptr<float>();
+  }
+  TORCH_CHECK(linear_wgrad_wide_runs(N, K, B),
+              "linear_wgrad_wide: unsupported (No, Ki, B); use linear_wgrad_into");
+  TORCH_CHECK(((uintptr_t)dz.data_ptr() & 15) == 0 && ((uintptr_t)x.data_ptr() & 15) == 0,
+              "linear_wgrad_wide wants 16-byte aligned dz and x");
+  CHECK_HIP(launch_linear_wgrad_wide((const bf16raw*)dz.data_ptr(), (const bf16raw*)x.data_ptr(),
+                                     dw.data_ptr<float>(), dbp, B, (int)N, (int)K,
+                                     (int)max_blocks, head_num_cus(), cur_stream()));
+}
+
 // One-pass backward of a hidden Linear on a ReLU output (hidden_bwd.hip):
 // returns dz_in = (dz @ w) * (x_in > 0), bit-identical to linear_dgrad_relu,
 // and accumulates dw / db under linear_wgrad_stream's contract.
@@ -1608,6 +1646,15 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("linear_wgrad_stream", &linear_wgrad_stream,
         "dW (+ db) accumulated by the persistent batch-streaming kernel", py::arg("dz"),
         py::arg("x"), py::arg("dw"), py::arg("db") = py::none(), py::arg("max_blocks") = 0);
+  m.def("linear_wgrad_wide_supported", &linear_wgrad_wide_ok,
+        "is (No, Ki) at batch B routed to the wide-layer streaming wgrad");
+  m.def("linear_wgrad_wide_can_run", &linear_wgrad_wide_runs,
+        "can the wide-layer streaming wgrad compute (No, Ki, B) at all");
+  m.def("linear_wgrad_wide", &linear_wgrad_wide,
+        "dW (+ db) of a wide layer on a 64/128/256-wide input, accumulated by its persistent "
+        "batch-streaming kernel",
+        py::arg("dz"), py::arg("x"), py::arg("dw"), py::arg("db") = py::none(),
+        py::arg("max_blocks") = 0);
   m.def("linear_hidden_bwd_supported", &linear_hidden_bwd_ok,
         "is (No, Ki) at batch B routed to the one-pass hidden-layer backward");
   m.def("linear_hidden_bwd_can_run", &linear_hidden_bwd_runs,

@@ -7,6 +7,9 @@ backward:
   dx = dz @ W                  — MFMA
   dW = dz^T @ x                — MFMA, split-K over batch (atomic fp32); big
                                  batches: persistent streaming kernel with db
+                                 (64/128/256 outputs: linear_wgrad.hip; more
+                                 than 256 outputs on a 64/128/256-wide input:
+                                 linear_wgrad_wide.hip)
   db = colsum(dz)              — bias_grad
 Layer stacks (hip_mlp_chain) fold the ReLU mask into the consumer's dgrad
 epilogue, give a big-batch hidden layer on a ReLU output its masked dgrad, dW
@@ -57,14 +60,35 @@ def _wgrad_stream_ok(ext, dz: torch.Tensor, x: torch.Tensor) -> bool:
     return B >= _WGRAD_STREAM_MIN_BATCH and ext.linear_wgrad_stream_can_run(n_out, k_in, B)
 
 
+# Tests flip this to keep a wide layer's wgrad on the split-K route.
+_WGRAD_WIDE = True
+# None: linear_wgrad_wide.hip's measured batch threshold.  Tests lower it to
+# drive small batches through that kernel.
+_WGRAD_WIDE_MIN_BATCH = None
+
+
+def _wgrad_wide_ok(ext, dz: torch.Tensor, x: torch.Tensor) -> bool:
+    if not (_WGRAD_WIDE and _WGRAD_STREAM) or dz.data_ptr() % 16 or x.data_ptr() % 16:
+        return False
+    B, n_out, k_in = dz.shape[0], dz.shape[1], x.shape[1]
+    if _WGRAD_WIDE_MIN_BATCH is None:
+        return ext.linear_wgrad_wide_supported(n_out, k_in, B)
+    return B >= _WGRAD_WIDE_MIN_BATCH and ext.linear_wgrad_wide_can_run(n_out, k_in, B)
+
+
 def linear_wgrad_into(dz, x, dw, db=None):
     """``dw += dz^T @ x`` and, with ``db``, ``db += colsum(dz)`` (fp32, the
     caller zeroes).  Big batches of a 64/128/256-output layer stream through
-    the persistent kernel (linear_wgrad.hip); everything else takes the
-    split-K gemm_kernel route."""
+    the persistent kernel (linear_wgrad.hip), and big batches of a layer with
+    more than 256 outputs (any multiple of 8) on a 64/128/256-wide input
+    through its mirror image (linear_wgrad_wide.hip); everything else takes
+    the split-K gemm_kernel route."""
     ext = ops.ext()
     if _wgrad_stream_ok(ext, dz, x):
         ext.linear_wgrad_stream(dz, x, dw, db, 0)
+        return
+    if _wgrad_wide_ok(ext, dz, x):
+        ext.linear_wgrad_wide(dz, x, dw, db, 0)
         return
     sk = _choose_splitk(dz.shape[0], dz.shape[1], x.shape[1])
     if db is not None:
