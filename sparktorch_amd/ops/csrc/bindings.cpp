@@ -88,6 +88,9 @@ int64_t mlp_predict_min_rows();
 hipError_t launch_mlp_predict(const bf16raw*, const bf16raw* const*, const float* const*,
                               const int*, int, int, int, int64_t, int*, bf16raw*, int, int,
                               hipStream_t);
+hipError_t launch_mlp_predict_f32(const float*, const bf16raw* const*, const float* const*,
+                                  const int*, int, int, int, int64_t, int*, bf16raw*, int, int,
+                                  hipStream_t);
 hipError_t launch_bn_stats(const bf16raw*, float*, float*, float*, float*, float*, float*, int,
                            int, int64_t, float, float, int, hipStream_t);
 hipError_t launch_bn_apply(const bf16raw*, const bf16raw*, bf16raw*, const float*, const float*,
@@ -831,7 +834,10 @@ int64_t mlp_predict_min_rows_py() { return mlp_predict_min_rows(); }
 std::tuple<at::Tensor, c10::optional<at::Tensor>> mlp_predict(
     at::Tensor x, std::vector<at::Tensor> weights, std::vector<c10::optional<at::Tensor>> biases,
     bool want_logits, int64_t max_blocks) {
-  check_gpu_contig(x, at::kBFloat16, "x");
+  // fp32 rows are read as they are (mlp_predict_kernel<true> rounds them as
+  // torch's cast would); the logits stay bf16
+  const bool x_f32 = x.scalar_type() == at::kFloat;
+  check_gpu_contig(x, x_f32 ? at::kFloat : at::kBFloat16, "x");
   TORCH_CHECK(x.dim() == 2, "x must be [M, K0]");
   TORCH_CHECK(weights.size() >= 2 && weights.size() <= 5,
               "mlp_predict: one to four hidden layers and a head");
@@ -871,11 +877,17 @@ std::tuple<at::Tensor, c10::optional<at::Tensor>> mlp_predict(
   TORCH_CHECK(aligned, "mlp_predict wants 16-byte aligned operands");
   auto classes = at::empty({M}, x.options().dtype(at::kInt));
   c10::optional<at::Tensor> logits;
-  if (want_logits) logits = at::empty({M, C}, x.options());
-  CHECK_HIP(launch_mlp_predict((const bf16raw*)x.data_ptr(), wp, bp, wv, L, (int)K0, (int)C, M,
-                               classes.data_ptr<int>(),
-                               want_logits ? (bf16raw*)logits->data_ptr() : nullptr,
-                               (int)max_blocks, head_num_cus(), cur_stream()));
+  if (want_logits) logits = at::empty({M, C}, x.options().dtype(at::kBFloat16));
+  bf16raw* lp = want_logits ? (bf16raw*)logits->data_ptr() : nullptr;
+  if (x_f32) {
+    CHECK_HIP(launch_mlp_predict_f32(x.data_ptr<float>(), wp, bp, wv, L, (int)K0, (int)C, M,
+                                     classes.data_ptr<int>(), lp, (int)max_blocks,
+                                     head_num_cus(), cur_stream()));
+  } else {
+    CHECK_HIP(launch_mlp_predict((const bf16raw*)x.data_ptr(), wp, bp, wv, L, (int)K0, (int)C, M,
+                                 classes.data_ptr<int>(), lp, (int)max_blocks, head_num_cus(),
+                                 cur_stream()));
+  }
   return {classes, logits};
 }
 
@@ -1636,7 +1648,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("mlp_predict_min_rows", &mlp_predict_min_rows_py,
         "rows from which MnistMLPFused.forward takes the one-launch inference kernel");
   m.def("mlp_predict", &mlp_predict,
-        "hidden layers + head + argmax in one launch: (classes int32, logits or None)",
+        "hidden layers + head + argmax in one launch from bf16 or fp32 rows: (classes int32, "
+        "bf16 logits or None)",
         py::arg("x"), py::arg("weights"), py::arg("biases"), py::arg("want_logits") = false,
         py::arg("max_blocks") = 0);
   m.def("linear_wgrad_stream_supported", &linear_wgrad_stream_ok,

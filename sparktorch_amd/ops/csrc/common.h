@@ -34,6 +34,24 @@ __device__ __forceinline__ bf16raw f32_to_bf16(float f) {
   return (bf16raw)(u >> 16);
 }
 
+// f32 -> bf16 of USER data (the cast kernels, mlp_predict.hip's fp32 rows):
+// it may carry NaNs with any payload, and the rounding add of f32_to_bf16
+// carries a low-payload NaN into Inf (0x7F800001) or across the sign into zero
+// (0x7FFFFFFF).  A NaN becomes a quiet NaN of the same sign here; everything
+// else rounds as there, which is what torch's cast stores.  The test is on the
+// bits: the build's -ffast-math folds x != x away.  (Arithmetic NaNs are
+// canonical 0x7FC00000 and survive f32_to_bf16, which the hot kernels keep.)
+__device__ __forceinline__ bf16raw cast_f32_to_bf16(float f) {
+  union {
+    float f;
+    uint32_t u;
+  } c;
+  c.f = f;
+  const uint32_t nan = (c.u >> 16) | 0x0040u;
+  const uint32_t rne = (c.u + 0x7fffu + ((c.u >> 16) & 1u)) >> 16;  // f32_to_bf16
+  return (bf16raw)((c.u & 0x7fffffffu) > 0x7f800000u ? nan : rne);
+}
+
 typedef float floatx4 __attribute__((ext_vector_type(4)));
 typedef float floatx16 __attribute__((ext_vector_type(16)));
 typedef short shortx8 __attribute__((ext_vector_type(8)));

@@ -422,23 +422,8 @@ extern "C" hipError_t launch_small_wgrad(const bf16raw* dz, const bf16raw* col, 
 // NaN-keeping conversions of the cast kernels
 // ---------------------------------------------------------------------------
 
-// f32 -> bf16 for the cast kernels only: user data may carry NaNs with any
-// payload, and the rounding add of common.h's f32_to_bf16 carries a low-payload
-// NaN into Inf (0x7F800001) or across the sign into zero (0x7FFFFFFF).  A NaN
-// becomes a quiet NaN of the same sign here; everything else rounds as there.
-// The test is on the bits: the build's -ffast-math folds x != x away.
-// (Arithmetic NaNs are canonical 0x7FC00000 and survive f32_to_bf16, which
-// the hot kernels keep.)
-__device__ __forceinline__ bf16raw cast_f32_to_bf16(float f) {
-  union {
-    float f;
-    uint32_t u;
-  } c;
-  c.f = f;
-  if ((c.u & 0x7fffffffu) > 0x7f800000u) return (bf16raw)((c.u >> 16) | 0x0040u);
-  return f32_to_bf16(f);
-}
-
+// f32 -> bf16 goes through common.h's cast_f32_to_bf16 (user data may carry
+// NaNs with any payload).
 // f64 -> f32 with NaN kept by a test on the bits, for the same reason.
 __device__ __forceinline__ float cast_f64_to_f32(double d) {
   union {

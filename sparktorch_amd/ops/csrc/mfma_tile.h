@@ -8,7 +8,8 @@
 //     global->LDS DMA (destination = wave-uniform base + lane * 16),
 //     bank-spread for the ds_read_b128 fragment reads.  The swizzle permutes
 //     16 B pieces inside one 128 B line of the source row, so global
-//     coalescing is kept;
+//     coalescing is kept; an fp32 operand reaches the same image through
+//     registers (mt_ldg_f32_kmajor / mt_sts_bf16_kmajor);
 //   * the k-packing of a fragment: lane (l15, kg) of a 16x16x32 MFMA operand
 //     holds row l15, k = 8kg .. 8kg+7 of the 32-wide step, whether it comes
 //     from a ds_read_b128 of a k-major image or from the transposing read of
@@ -123,6 +124,51 @@ __device__ __forceinline__ void mt_fill_kmajor(const bf16raw* __restrict__ src,
     if (row0 + row < rmax && k < kmax) v = *(const shortx8*)(src + (row0 + row) * ld + k);
     *(shortx8*)(lds + u * 8) = v;
   }
+}
+
+// ---- fp32 source -> the same image, through registers ----
+//
+// The DMA cannot convert, so an fp32 operand is staged in two halves with any
+// number of steps between them: mt_ldg_f32_kmajor puts the 8 floats of image
+// slot u (16 B of bf16) into 8 VGPRs by two global_load_dwordx4, and
+// mt_sts_bf16_kmajor rounds them (cast_f32_to_bf16: what torch's cast stores,
+// NaN kept) and writes the slot with one ds_write_b128, exactly where
+// mt_dma_kmajor / mt_fill_kmajor put it.  u runs over ROWS * BKT / 8 slots;
+// rows at or past rmax and k at or past kmax are zero in the image.  The load
+// half ALWAYS issues its two instructions for every lane (a slot outside the
+// operand reads src[0 .. 7], which exists, and the store half drops it), so a
+// caller with counted vmcnt waits knows what a slab costs.  src must be 16 B
+// aligned and ld a multiple of 8.
+template <int BKT, typename KEY = mt_key_row>
+__device__ __forceinline__ bool mt_f32_slot(int u, int64_t row0, int64_t rmax, int kt, int kmax,
+                                            int& row, int& k) {
+  constexpr int SLOTS = BKT / 8;
+  row = u / SLOTS;
+  k = kt + (((u % SLOTS) ^ KEY::template key<SLOTS>(row)) << 3);
+  return row0 + row < rmax && k < kmax;
+}
+
+template <int BKT, typename KEY = mt_key_row>
+__device__ __forceinline__ void mt_ldg_f32_kmajor(floatx4 (&v)[2], const float* src, int64_t row0,
+                                                  int64_t rmax, int64_t ld, int kt, int kmax,
+                                                  int u) {
+  int row, k;
+  const bool ok = mt_f32_slot<BKT, KEY>(u, row0, rmax, kt, kmax, row, k);
+  const float* g = ok ? src + (row0 + row) * ld + k : src;
+  v[0] = *(const floatx4*)g;
+  v[1] = *(const floatx4*)(g + 4);
+}
+
+template <int BKT, typename KEY = mt_key_row>
+__device__ __forceinline__ void mt_sts_bf16_kmajor(const floatx4 (&v)[2], bf16raw* lds,
+                                                   int64_t row0, int64_t rmax, int kt, int kmax,
+                                                   int u) {
+  int row, k;
+  const bool ok = mt_f32_slot<BKT, KEY>(u, row0, rmax, kt, kmax, row, k);
+  shortx8 o;
+#pragma unroll
+  for (int j = 0; j < 8; ++j) o[j] = (short)cast_f32_to_bf16(v[j >> 2][j & 3]);
+  *(shortx8*)(lds + u * 8) = ok ? o : shortx8{};
 }
 
 // ---- fragments ----

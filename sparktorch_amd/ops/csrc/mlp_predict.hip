@@ -1,4 +1,4 @@
-// Whole-MLP inference in one launch: bf16 rows x[M,K0] go through L hidden
+// Whole-MLP inference in one launch: bf16 (or fp32) rows x[M,K0] go through L hidden
 // layers h_l = relu(h_{l-1} W_l^T + b_l) and a small head
 // logits = h_L W_h^T + b_h (C <= 16 classes); the kernel writes each row's
 // class id (int32 argmax of the bf16 logits) and, when asked, the logits.
@@ -46,6 +46,47 @@
 // LDS: 40 KB A ring + 48 KB W ring + 64 KB image + 4 KB biases = 156 KB, one
 // block per CU.  Widths 64 / 128 / 192 leave wave columns idle in that layer
 // (they still help staging).
+//
+// fp32 rows (mlp_predict_kernel<true>).  Every public inference path holds
+// fp32 features; casting them first is a pass that reads 4 and writes 2 bytes
+// an element before this kernel reads the 2 back.  The X_F32 instantiation
+// reads the fp32 rows itself.  The DMA cannot convert, so layer 1's A operand
+// goes through registers (mfma_tile.h, mt_ldg_f32_kmajor / mt_sts_bf16_kmajor):
+//   * a slab is 128 rows x 32 k = 512 image slots of 16 B, one per thread:
+//     two global_load_dwordx4 (32 contiguous bytes of one row; the four
+//     threads of a row cover one 128 B line), eight roundings with torch's
+//     cast rule (cast_f32_to_bf16), one ds_write_b128 to the slot the DMA
+//     would have filled.  The image is identical, so mt_ld_frag, the MFMA
+//     loop, the epilogues, layers 2..L, the head and the argmax are shared
+//     code and the logits are bit-identical to cast + the bf16 kernel;
+//   * slab s + MP_XD is loaded in step s and stays in 8 VGPRs until step
+//     s + MP_XD - 1 converts it into the next of the ring's first four slots,
+//     which the barrier of that step publishes for the step after
+//     (lgkmcnt(0) is part of every mp_publish).  The k-loop is unrolled MP_XD
+//     times so that slab s lives in the statically named registers
+//     xr[s % MP_XD];
+//   * out-of-range slots (rows past M, the K tail) load x[0 .. 7] instead and
+//     are zeroed at the store: every wave issues exactly MP_X_LD loads per
+//     slab, whatever the edge;
+//   * vmcnt retires the register loads and the W DMAs in order.  A step
+//     multiplies, converts x(s + 1), then issues W(s + 2) [MP_W_DMA, or none
+//     when that slab is a zero-filled tail] and x(s + MP_XD) [MP_X_LD], with
+//     compiler barriers that keep that order.  Its closing barrier needs
+//     W(s + 1), issued in step s - 1 ahead of x(s - 1 + MP_XD); what may still
+//     be in flight is that x slab, W(s + 2) and x(s + MP_XD): up to 6
+//     instructions.  The wait before the conversion is the compiler's, and
+//     with LDS DMAs in the queue it treats the queue as unordered and emits
+//     vmcnt(0): every load of step s - 1 has landed when step s converts.
+//     That is why the issues come AFTER the conversion (they get a whole step
+//     to land) and why MP_XD = 2 is as deep as x can usefully run; the counted
+//     waits do not rely on that drain;
+//   * the 32 VGPRs of head-weight fragments move to the ring's fifth slot
+//     (the x registers and the conversion need the room: no scratch), and
+//     the head reads them back with ds_read_b128;
+//   * once layer 1's k-loop is done the next tile's first MP_XD slabs are
+//     loaded into xr[] and ride in registers under the hidden layers and the
+//     head (whose mp_publish(0) waits merely land them early); the next tile
+//     starts by converting slab 0.
 
 #include "mfma_tile.h"
 
@@ -59,8 +100,13 @@
 #define MP_MAX_HIDDEN 4
 #define MP_CMAX 16
 
+#ifndef MP_XD
+#define MP_XD 2  // fp32 rows: slab s + 2 is loaded (to registers) in step s
+#endif
+#define MP_X_LD 2  // global_load_dwordx4 a wave issues per fp32 slab
+
 struct MlpPredictArgs {
-  const bf16raw* x;
+  const void* x;  // bf16 rows, or fp32 rows for mlp_predict_kernel<true>
   const bf16raw* w[MP_MAX_HIDDEN + 1];  // hidden layers, then the head
   const float* b[MP_MAX_HIDDEN + 1];    // nullptr = no bias
   int n[MP_MAX_HIDDEN];                 // hidden widths
@@ -78,8 +124,11 @@ struct MlpPredictArgs {
 // and writes; then the block's barrier.  __syncthreads() would drain the
 // DMAs that are meant to stay in flight.
 __device__ __forceinline__ void mp_publish(int newer) {
-  static_assert(MP_A_DMA == 1 && MP_W_DMA == 2, "the cases below are written for these counts");
+  static_assert(MP_A_DMA == 1 && MP_W_DMA == 2 && MP_X_LD == 2,
+                "the cases below are written for these counts");
   switch (newer) {
+    case 6: mt_wait_barrier<6>(); break;
+    case 5: mt_wait_barrier<5>(); break;
     case 4: mt_wait_barrier<4>(); break;
     case 3: mt_wait_barrier<3>(); break;
     case 2: mt_wait_barrier<2>(); break;
@@ -88,7 +137,10 @@ __device__ __forceinline__ void mp_publish(int newer) {
   }
 }
 
+template <bool X_F32>
 __global__ __launch_bounds__(MP_THREADS, 2) void mlp_predict_kernel(const MlpPredictArgs p) {
+  static_assert(MP_XD >= 2 && MP_XD <= 4, "x slabs held in registers, 8 VGPRs each");
+  static_assert(MP_THREADS == MP_BM * MP_BK / 8, "fp32 staging: one image slot per thread");
   constexpr int BKT = MP_BK;
   constexpr int SLOTS = BKT / 8;
   constexpr int A_EL = MP_BM * BKT, B_EL = MP_BN * BKT;
@@ -121,6 +173,19 @@ __global__ __launch_bounds__(MP_THREADS, 2) void mlp_predict_kernel(const MlpPre
   const bf16raw* const wh = p.w[L];
   mt_frag_t wk[MP_BN / 32];
   mt_head_w_frags(wk, wh, H, C, l15, kg);
+  // fp32 rows: the x registers need the room, so the fragments (the same in
+  // every wave) live in the A ring's last slot, [ks][lane] x 16 B, and the
+  // head reads them back; x goes through the NAX slots before it.  Published
+  // by the first barrier below.
+  constexpr int NAX = MP_NA - 1;
+  bf16raw* const wk_lds = a_ring + NAX * A_EL;
+  static_assert(MP_BN / 32 * 64 * 8 <= A_EL, "the head's fragments fit one ring slot");
+  if constexpr (X_F32) {
+    if (wid == 0) {
+#pragma unroll
+      for (int ks = 0; ks < MP_BN / 32; ++ks) *(mt_frag_t*)(wk_lds + (ks * 64 + lane) * 8) = wk[ks];
+    }
+  }
   const bool head_bias = p.b[L] != nullptr;
   float bias_c = 0.f;
   if (head_bias && l15 < C) bias_c = p.b[L][l15];
@@ -128,13 +193,23 @@ __global__ __launch_bounds__(MP_THREADS, 2) void mlp_predict_kernel(const MlpPre
   // x slab kt of the tile at m0 -> ring slot; true when it went by DMA
   // (MP_A_DMA instructions per wave, in flight)
   auto stage_a = [&](int slot, int64_t m0, int kt) -> bool {
+    const bf16raw* xb = (const bf16raw*)p.x;
     bf16raw* an = a_ring + slot * A_EL;
     if (m0 + MP_BM <= M && kt + BKT <= K0) {
-      mt_dma_kmajor<MP_WAVES, MP_BM, BKT, true>(p.x, an, m0, MP_BM, K0, kt, wid, lane);
+      mt_dma_kmajor<MP_WAVES, MP_BM, BKT, true>(xb, an, m0, MP_BM, K0, kt, wid, lane);
       return true;
     }
-    mt_fill_kmajor<MP_THREADS, MP_BM, BKT>(p.x, an, m0, M, K0, kt, K0, t);
+    mt_fill_kmajor<MP_THREADS, MP_BM, BKT>(xb, an, m0, M, K0, kt, K0, t);
     return false;
+  };
+  // fp32 rows: x slab kt of the tile at m0 -> 8 registers (MP_X_LD loads per
+  // wave, always), and later from them -> ring slot
+  floatx4 xr[X_F32 ? MP_XD : 1][2] = {};
+  auto load_x = [&](floatx4(&r)[2], int64_t m0, int kt) {
+    mt_ldg_f32_kmajor<BKT>(r, (const float*)p.x, m0, M, K0, kt, K0, t);
+  };
+  auto store_x = [&](const floatx4(&r)[2], int slot, int64_t m0, int kt) {
+    mt_sts_bf16_kmajor<BKT>(r, a_ring + slot * A_EL, m0, M, kt, K0, t);
   };
   // W[N][K] slab kt -> ring slot; true when it went by DMA (MP_W_DMA per wave)
   auto stage_b = [&](int slot, const bf16raw* W, int N, int K, int kt) -> bool {
@@ -207,7 +282,59 @@ __global__ __launch_bounds__(MP_THREADS, 2) void mlp_predict_kernel(const MlpPre
     const int64_t m0_next = (int64_t)next * MP_BM;
 
     // ---- layer 1: x from HBM ----
-    {
+    if constexpr (X_F32) {
+      const bf16raw* W = p.w[0];
+      const int N = p.n[0], K = K0;
+      const bool active = wc * 64 < N;
+      zero_acc();
+      if (!staged) {
+#pragma unroll
+        for (int j = 0; j < MP_XD; ++j)
+          if (j * BKT < K) load_x(xr[j], m0, j * BKT);
+#pragma unroll
+        for (int j = 0; j < MP_NW - 1; ++j)
+          if (j * BKT < K) stage_b(j, W, N, K, j * BKT);
+      }  // else: issued under the tile before, which also waited for them
+      store_x(xr[0], 0, m0, 0);
+      mp_publish(0);
+      // Step on slab kt (ring slots ia / ib; x slab kt came from xr[j]):
+      // multiply, convert x(kt+1) into the ring slot after ia, issue W(kt+2)
+      // THEN load x(kt+MP_XD) into xr[j], publish.  The counts are in the header.
+      int ia = 0, ib = 0;
+      bool x_prev = false;
+      for (int kt0 = 0; kt0 < K; kt0 += MP_XD * BKT) {
+#pragma unroll
+        for (int j = 0; j < MP_XD; ++j) {
+          const int kt = kt0 + j * BKT;
+          if (kt < K) {
+            int newer = x_prev ? MP_X_LD : 0;
+            mma(a_ring + ia * A_EL, b_ring + ib * B_EL, kt, false, active);
+            ia = ia == NAX - 1 ? 0 : ia + 1;
+            if (kt + BKT < K) store_x(xr[(j + 1) % MP_XD], ia, m0, kt + BKT);
+            asm volatile("" ::: "memory");  // the conversion's wait stays ahead of the issues
+            if (kt + (MP_NW - 1) * BKT < K) {
+              const int slot = ib == 0 ? MP_NW - 1 : ib - 1;
+              if (stage_b(slot, W, N, K, kt + (MP_NW - 1) * BKT)) newer += MP_W_DMA;
+            }
+            asm volatile("" ::: "memory");  // W's DMAs stay ahead of x's loads
+            x_prev = kt + MP_XD * BKT < K;
+            if (x_prev) {
+              load_x(xr[j], m0, kt + MP_XD * BKT);
+              newer += MP_X_LD;
+            }
+            ib = ib == MP_NW - 1 ? 0 : ib + 1;
+            mp_publish(newer);
+          }
+        }
+      }
+      // Every x register is free.  The next tile's first slabs are loaded now
+      // and ride in them under the hidden layers.
+      if (next < ntiles) {
+#pragma unroll
+        for (int j = 0; j < MP_XD; ++j)
+          if (j * BKT < K0) load_x(xr[j], m0_next, j * BKT);
+      }
+    } else {
       const bf16raw* W = p.w[0];
       const int N = p.n[0], K = K0;
       const bool active = wc * 64 < N;
@@ -246,13 +373,13 @@ __global__ __launch_bounds__(MP_THREADS, 2) void mlp_predict_kernel(const MlpPre
         ia = ia == MP_NA - 1 ? 0 : ia + 1;
         ib = ib == MP_NW - 1 ? 0 : ib + 1;
       }
-    }
-    // Every ring slot is idle (closing barrier above).  The next tile's first
-    // A slabs go in flight now and land under the hidden layers.
-    if (next < ntiles) {
+      // Every ring slot is idle (closing barrier above).  The next tile's first
+      // A slabs go in flight now and land under the hidden layers.
+      if (next < ntiles) {
 #pragma unroll
-      for (int j = 0; j < MP_NA - 1; ++j)
-        if (j * BKT < K0) stage_a(j, m0_next, j * BKT);
+        for (int j = 0; j < MP_NA - 1; ++j)
+          if (j * BKT < K0) stage_a(j, m0_next, j * BKT);
+      }
     }
 
     // ---- epilogue of layer l, then layer l + 1 from the image ----
@@ -293,7 +420,11 @@ __global__ __launch_bounds__(MP_THREADS, 2) void mlp_predict_kernel(const MlpPre
     // ---- head: logits of rows wid*16 .. +15 from the image, argmax ----
     {
       const int arow = wid * 16 + l15;
-      const floatx4 lg = mt_head_logits<MP_BN / 32, MP_BN, IMG_XM>(wk, img, arow, H, kg);
+      mt_frag_t wh_f[MP_BN / 32];
+#pragma unroll
+      for (int ks = 0; ks < MP_BN / 32; ++ks)
+        wh_f[ks] = X_F32 ? *(const mt_frag_t*)(wk_lds + (ks * 64 + lane) * 8) : wk[ks];
+      const floatx4 lg = mt_head_logits<MP_BN / 32, MP_BN, IMG_XM>(wh_f, img, arow, H, kg);
       // lane (class l15, kg), element r <-> tile row wid*16 + kg*4 + r
       int best[4];
 #pragma unroll
@@ -342,13 +473,10 @@ extern "C" int mlp_predict_supported(int K0, const int* widths, int L, int C, in
 #define MP_MIN_ROWS 4096
 extern "C" int64_t mlp_predict_min_rows() { return MP_MIN_ROWS; }
 
-// w / b: L hidden layers then the head (b entries may be null); max_blocks > 0
-// caps the persistent grid (tests force several tiles per block with it).
-// All pointers 16-byte aligned.
-extern "C" hipError_t launch_mlp_predict(const bf16raw* x, const bf16raw* const* w,
-                                         const float* const* b, const int* widths, int L, int K0,
-                                         int C, int64_t M, int* classes, bf16raw* logits,
-                                         int max_blocks, int num_cus, hipStream_t stream) {
+template <bool X_F32>
+static hipError_t mp_launch(const void* x, const bf16raw* const* w, const float* const* b,
+                            const int* widths, int L, int K0, int C, int64_t M, int* classes,
+                            bf16raw* logits, int max_blocks, int num_cus, hipStream_t stream) {
   if (!mlp_predict_supported(K0, widths, L, C, M)) return hipErrorInvalidValue;
   if (x == nullptr || classes == nullptr || w == nullptr || b == nullptr)
     return hipErrorInvalidValue;
@@ -373,7 +501,29 @@ extern "C" hipError_t launch_mlp_predict(const bf16raw* x, const bf16raw* const*
   int64_t grid = num_cus > 0 ? num_cus : 256;  // 156 KB of LDS: one block per CU
   if (max_blocks > 0 && grid > max_blocks) grid = max_blocks;
   if (grid > ntiles) grid = ntiles;
-  mlp_predict_kernel<<<dim3((unsigned)grid), dim3(MP_THREADS), 0, stream>>>(a);
+  mlp_predict_kernel<X_F32><<<dim3((unsigned)grid), dim3(MP_THREADS), 0, stream>>>(a);
   HIP_CHECK_LAUNCH();
   return hipSuccess;
+}
+
+// w / b: L hidden layers then the head (b entries may be null); max_blocks > 0
+// caps the persistent grid (tests force several tiles per block with it).
+// All pointers 16-byte aligned.
+extern "C" hipError_t launch_mlp_predict(const bf16raw* x, const bf16raw* const* w,
+                                         const float* const* b, const int* widths, int L, int K0,
+                                         int C, int64_t M, int* classes, bf16raw* logits,
+                                         int max_blocks, int num_cus, hipStream_t stream) {
+  return mp_launch<false>(x, w, b, widths, L, K0, C, M, classes, logits, max_blocks, num_cus,
+                          stream);
+}
+
+// the same from fp32 rows x[M][K0] (rounded to bf16 as torch's cast rounds
+// them); everything else as above, the weights stay bf16
+extern "C" hipError_t launch_mlp_predict_f32(const float* x, const bf16raw* const* w,
+                                             const float* const* b, const int* widths, int L,
+                                             int K0, int C, int64_t M, int* classes,
+                                             bf16raw* logits, int max_blocks, int num_cus,
+                                             hipStream_t stream) {
+  return mp_launch<true>(x, w, b, widths, L, K0, C, M, classes, logits, max_blocks, num_cus,
+                         stream);
 }

@@ -376,6 +376,9 @@ def hip_mlp_chain(x: torch.Tensor, layers) -> torch.Tensor:
 
 # Tests flip this to force the per-layer chain + argmax for hip_mlp_predict.
 _PREDICT_FUSION = True
+# Tests flip this to cast an fp32 x to bf16 before the one-launch kernel
+# instead of letting the kernel read the fp32 rows.
+_PREDICT_F32 = True
 
 
 def _mlp_predict_ok(x: torch.Tensor, layers) -> bool:
@@ -413,12 +416,19 @@ def hip_mlp_predict(x: torch.Tensor, layers, want_logits: bool = False, max_bloc
     output, or ``None`` unless ``want_logits``.  GPU: one launch
     (mlp_predict.hip) that reads x once and keeps the hidden activations in
     LDS, where it serves the chain; the logits are bit-identical to
-    hip_mlp_chain's.  Anything else (CPU, an unsupported width or class
-    count, a hidden layer without ReLU, a head with one, more than four
-    hidden layers, misaligned operands) runs hip_mlp_chain and torch.argmax."""
+    hip_mlp_chain's.  A contiguous, 16 B-aligned fp32 ``x`` is handed to the
+    kernel as it is (it rounds the rows to bf16 itself, as ``x.to(bfloat16)``
+    would); any other non-bf16 ``x`` is cast first.  Anything else (CPU, an
+    unsupported width or class count, a hidden layer without ReLU, a head with
+    one, more than four hidden layers, misaligned operands) runs hip_mlp_chain
+    and torch.argmax."""
     if x.is_cuda and x.dim() == 2 and _mlp_predict_ok(x, layers):
         ext = ops.ext()
-        xb = x if x.dtype == torch.bfloat16 else x.to(torch.bfloat16)
+        if (_PREDICT_F32 and x.dtype == torch.float32 and x.is_contiguous()
+                and x.data_ptr() % 16 == 0):
+            xb = x  # the kernel reads fp32 rows: no cast pass
+        else:
+            xb = x if x.dtype == torch.bfloat16 else x.to(torch.bfloat16)
         if not xb.is_contiguous():
             xb = xb.contiguous()
         ws = [(ext.cast_f32_bf16(w) if w.dtype == torch.float32 else w).contiguous()

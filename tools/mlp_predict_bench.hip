@@ -3,10 +3,13 @@
 // routes a layer there (N in (128, 256], M >= its row threshold), else
 // gemm.hip's tiles.
 // hipcc --offload-arch=gfx950 -O3 -ffast-math tools/mlp_predict_bench.hip -o tools/mlp_predict_bench
-// usage: mlp_predict_bench [--dims K0,w1[,w2..],C] [M ...]   (default 784,256,256,10 at 2097152)
+// usage: mlp_predict_bench [--f32] [--dims K0,w1[,w2..],C] [M ...]   (default 784,256,256,10 at 2097152)
 // Prints us per launch (fused; the per-layer launches and their sum), TB/s of
 // NEEDED bytes (x once + 4 B of class id a row), and whether the logits are
 // bit-identical and the class ids the argmax of the per-layer logits.
+// --f32: fp32 rows instead, cast + bf16 kernel against the fp32-input kernel
+// (run_f32 below).
+#include "../sparktorch_amd/ops/csrc/elementwise.hip"
 #include "../sparktorch_amd/ops/csrc/gemm.hip"
 #include "../sparktorch_amd/ops/csrc/linear_stream.hip"
 #include "../sparktorch_amd/ops/csrc/mlp_predict.hip"
@@ -40,11 +43,84 @@ static float bf16_host(bf16raw h) {
   return f;
 }
 
+// fp32 rows with full 23-bit mantissas (almost none bf16-exact), |x| < 1
+__global__ void fill_x_f32_kernel(float* p, int64_t n, uint32_t seed) {
+  for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n;
+       i += (int64_t)gridDim.x * blockDim.x) {
+    uint32_t h = (uint32_t)i * 2654435761u ^ (uint32_t)(i >> 32) * 40503u ^ seed;
+    h ^= h >> 15; h *= 2246822519u; h ^= h >> 13;
+    p[i] = ((int)(h & 0xFFFFFF) - 0x800000) / 8388608.f;
+  }
+}
+
+// --f32: fp32 rows.  The route being replaced (cast_f32_bf16_kernel of
+// elementwise.hip, then the bf16 kernel) against mlp_predict_kernel<true>
+// alone, REPS timed launches each after WARM, logits and class ids of the two
+// compared bit for bit over all rows.
+static int run_f32(const std::vector<int>& dims, int64_t M, int num_cus) {
+  const int NL = (int)dims.size() - 1, L = NL - 1, K0 = dims[0], C = dims[NL];
+  const int WARM = 2, REPS = 10;
+  float* xf;
+  bf16raw *xb, *w[MP_MAX_HIDDEN + 1], *lg[2];
+  float* b[MP_MAX_HIDDEN + 1];
+  int* cls[2];
+  CKB(hipMalloc(&xf, M * K0 * 4));
+  CKB(hipMalloc(&xb, M * K0 * 2));
+  fill_x_f32_kernel<<<2048, 256>>>(xf, M * K0, 1u);
+  for (int l = 0; l < NL; ++l) {
+    const int K = dims[l], N = dims[l + 1];
+    CKB(hipMalloc(&w[l], (size_t)K * N * 2));
+    CKB(hipMalloc(&b[l], ((N * 4 + 15) / 16) * 16));
+    fill_kernel<<<64, 256>>>(w[l], (int64_t)K * N, 2u + l, 2.f / sqrtf((float)K));
+    fill_f32_kernel<<<1, 256>>>(b[l], N, 9u + l);
+  }
+  for (int r = 0; r < 2; ++r) {
+    CKB(hipMalloc(&lg[r], M * C * 2));
+    CKB(hipMalloc(&cls[r], M * 4));
+  }
+  CKB(hipDeviceSynchronize());
+  hipEvent_t e0, e1; CKB(hipEventCreate(&e0)); CKB(hipEventCreate(&e1));
+  // v = 0: cast alone, 1: bf16 kernel alone, 2: cast then bf16 kernel, 3: fp32 kernel
+  float us[4];
+  for (int v = 0; v < 4; ++v) {
+    for (int it = 0; it < WARM + REPS; ++it) {
+      if (it == WARM) CKB(hipEventRecord(e0));
+      if (v == 0 || v == 2) CKB(launch_cast_f32_bf16(xf, xb, M * K0, 0));
+      if (v == 1 || v == 2)
+        CKB(launch_mlp_predict(xb, w, b, &dims[1], L, K0, C, M, cls[0], lg[0], 0, num_cus, 0));
+      if (v == 3)
+        CKB(launch_mlp_predict_f32(xf, w, b, &dims[1], L, K0, C, M, cls[1], lg[1], 0, num_cus, 0));
+    }
+    CKB(hipEventRecord(e1)); CKB(hipEventSynchronize(e1));
+    float t; CKB(hipEventElapsedTime(&t, e0, e1));
+    us[v] = t * 1000.f / REPS;
+  }
+  std::vector<bf16raw> h0(M * C), h1(M * C);
+  std::vector<int> c0(M), c1(M);
+  CKB(hipMemcpy(h0.data(), lg[0], M * C * 2, hipMemcpyDeviceToHost));
+  CKB(hipMemcpy(h1.data(), lg[1], M * C * 2, hipMemcpyDeviceToHost));
+  CKB(hipMemcpy(c0.data(), cls[0], M * 4, hipMemcpyDeviceToHost));
+  CKB(hipMemcpy(c1.data(), cls[1], M * 4, hipMemcpyDeviceToHost));
+  const bool same = memcmp(h0.data(), h1.data(), M * C * 2) == 0;
+  const bool ids = memcmp(c0.data(), c1.data(), M * 4) == 0;
+  printf("M=%8ld cast %8.1f us + bf16 kernel %8.1f us | cast+kernel %8.1f us | fp32 kernel %8.1f us"
+         "  %5.2f TB/s needed  %s %s\n", (long)M, us[0], us[1], us[2], us[3],
+         (double)M * (K0 * 4 + 4 + C * 2) / us[3] / 1e6, same ? "bits==cast route" : "BITS DIFFER",
+         ids ? "ids==cast route" : "IDS DIFFER");
+  (void)hipFree(xf); (void)hipFree(xb);
+  for (int l = 0; l < NL; ++l) { (void)hipFree(w[l]); (void)hipFree(b[l]); }
+  for (int r = 0; r < 2; ++r) { (void)hipFree(lg[r]); (void)hipFree(cls[r]); }
+  return same && ids ? 0 : 2;
+}
+
 int main(int argc, char** argv) {
   std::vector<int64_t> ms;
   std::vector<int> dims = {784, 256, 256, 10};
+  bool f32 = false;
   for (int i = 1; i < argc; ++i) {
-    if (!strcmp(argv[i], "--dims") && i + 1 < argc) {
+    if (!strcmp(argv[i], "--f32")) {
+      f32 = true;
+    } else if (!strcmp(argv[i], "--dims") && i + 1 < argc) {
       dims.clear();
       for (char* tok = strtok(argv[++i], ","); tok; tok = strtok(nullptr, ",")) dims.push_back(atoi(tok));
     } else {
@@ -60,6 +136,10 @@ int main(int argc, char** argv) {
   const int WARM = 2, REPS = 10;
   for (int64_t M : ms) {
     if (!mlp_predict_supported(K0, &dims[1], L, C, M)) { printf("unsupported chain\n"); return 1; }
+    if (f32) {
+      if (int rc = run_f32(dims, M, num_cus)) return rc;
+      continue;
+    }
     bf16raw *x, *w[MP_MAX_HIDDEN + 1], *act[MP_MAX_HIDDEN + 1], *logits;
     float* b[MP_MAX_HIDDEN + 1];
     int* classes;
