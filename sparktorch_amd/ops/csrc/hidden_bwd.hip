@@ -13,7 +13,9 @@
 //     and walks the 32-row batch tiles of its row group, persistent, dW / db
 //     in registers, flushed by fp32 atomicAdd at the end and once half-way
 //     through a long walk; the column tiles of a row group share an XCD.
-//     That is linear_wgrad_kernel's contract, rule for rule;
+//     That is linear_wgrad_kernel's contract, rule for rule, and each rule is
+//     linear_wgrad_tile.h's code: the images, the block deal, the walk's plan,
+//     the dW / db accumulate and flush, the grid plan;
 //   * the full-width dz tile and the ct slice of x that the block stages for
 //     dW are the operands of dz_in[rows, ct] = dz[rows, :] @ W[:, ct] and its
 //     mask as well.  Wave w owns output columns 16w .. 16w+15 of the slice:
@@ -58,9 +60,10 @@ __global__ __launch_bounds__(HB_THREADS, 1) void hidden_bwd_kernel(
   constexpr int ZSLOTS = NO / 8;
   constexpr int XSLOTS = LWG_XCOLS / 8;
   constexpr int Z_EL = LWG_ROWS * NO, X_EL = LWG_ROWS * LWG_XCOLS, O_EL = LWG_ROWS * HB_OPAD;
-  // DMA instructions a wave issues for one tile (1 KB chunks dealt evenly)
-  constexpr int Z_DMA = Z_EL * 2 / 1024 / HB_WAVES;
-  constexpr int X_DMA = X_EL * 2 / 1024 / HB_WAVES;
+  using ZI = lwg_row_image<ZSLOTS, HB_WAVES>;    // dz: whole rows
+  using XI = lwg_slice_image<XSLOTS, HB_WAVES>;  // x: the block's column tile
+  // DMA instructions a wave issues for one tile
+  constexpr int Z_DMA = ZI::DMA, X_DMA = XI::DMA;
   static_assert(RF == 1 || RF == 2, "No must be 128 or 256");
   static_assert(NF >= 1 && NF <= HB_WAVES && NF * 16 <= LWG_XCOLS, "one wave per dz_in fragment");
   static_assert(Z_DMA >= 1 && X_DMA == 1, "every wave stages part of both images");
@@ -83,40 +86,18 @@ __global__ __launch_bounds__(HB_THREADS, 1) void hidden_bwd_kernel(
   const int wid = __builtin_amdgcn_readfirstlane(t >> 6), lane = t & 63;
   const int l15 = lane & 15, q = lane >> 4;
 
-  // block id -> (row group, column tile), as linear_wgrad_kernel
   int grp, ct;
-  if (xcd_deal) {
-    const int xcd = blockIdx.x & 7, j = blockIdx.x >> 3;
-    grp = (j / ncol) * 8 + xcd;
-    ct = j % ncol;
-  } else {
-    grp = blockIdx.x / ncol;
-    ct = blockIdx.x % ncol;
-  }
+  lwg_block_deal(ncol, xcd_deal, grp, ct);
   const int nfull = B / LWG_ROWS;   // full tiles: DMA, no bounds to check
   const int kslots = Ki >> 3;       // 16 B slots per x row
   const int slot0 = ct * (NF * 2);  // first slot of this column tile
 
-  // DMA source offsets.  Wave w issues chunks w, w + 8, ...: a lane's row
-  // advances by a multiple of 8 from one of its chunks to the next, so its
-  // swizzle key stays and one lane offset serves all of them.
-  constexpr int ZRPC = 64 / ZSLOTS, XRPC = 64 / XSLOTS;
-  static_assert((HB_WAVES * ZRPC) % 8 == 0, "key must not depend on the chunk");
-  const int zr0 = wid * ZRPC + lane / ZSLOTS;
-  const unsigned zoff = zr0 * NO + (((lane % ZSLOTS) ^ lwg_key<ZSLOTS>::key(zr0)) << 3);
-  const int xr0 = wid * XRPC + lane / XSLOTS;
-  int xgs = slot0 + ((lane % XSLOTS) ^ lwg_key<XSLOTS>::key(xr0));
-  if (xgs > kslots - 1) xgs = kslots - 1;
-  const unsigned xoff = xr0 * Ki + xgs * 8;
-
+  const unsigned zoff = ZI::lane_off(wid, lane);
+  const unsigned xoff = XI::lane_off(wid, lane, Ki, slot0, kslots);
   auto stage = [&](bf16raw* zn, bf16raw* xn, int tile) {
     const int64_t row0 = (int64_t)tile * LWG_ROWS;
-#pragma unroll
-    for (int i = 0; i < Z_DMA; ++i) {
-      const bf16raw* g = dz + (row0 + i * HB_WAVES * ZRPC) * NO;
-      mt_glds16(g + zoff, zn + (wid + HB_WAVES * i) * 512);
-    }
-    mt_glds16(x + row0 * Ki + xoff, xn + wid * 512);
+    ZI::dma(dz, zn, row0, zoff, wid);
+    XI::dma(x, xn, row0, xoff, wid, Ki);
   };
   // End of a step: the tile after this one has landed in every wave's share
   // and every wave is done with this one.  The tile staged in this step is
@@ -156,22 +137,7 @@ __global__ __launch_bounds__(HB_THREADS, 1) void hidden_bwd_kernel(
 
   // dW / db: wave w owns dW rows 16 RF w .. + 16 RF - 1
   auto mma = [&](const bf16raw* zb, const bf16raw* xb) {
-    mt_frag_t az[RF];
-#pragma unroll
-    for (int a = 0; a < RF; ++a)
-      az[a] = lwg_tr_frag<ZSLOTS>(zb, q, l15, (wid * RF + a) * 16);
-    if (do_db) {
-#pragma unroll
-      for (int a = 0; a < RF; ++a)
-        accb[a] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(az[a], ones, accb[a], 0, 0, 0);
-    }
-#pragma unroll
-    for (int f = 0; f < NF; ++f) {
-      const mt_frag_t bx = lwg_tr_frag<XSLOTS>(xb, q, l15, f * 16);
-#pragma unroll
-      for (int a = 0; a < RF; ++a)
-        acc[a][f] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(az[a], bx, acc[a][f], 0, 0, 0);
-    }
+    lwg_accumulate<RF, NF, ZSLOTS>(acc, accb, zb, xb, ones, do_db, wid, q, l15);
   };
 
   // dz_in[32 rows][16 wid .. + 15] of the tile in (zb, xb) -> ob, bf16.
@@ -236,37 +202,14 @@ __global__ __launch_bounds__(HB_THREADS, 1) void hidden_bwd_kernel(
     publish(in_flight);
     tile += groups;
   };
-  // flush: accumulator lane (l15, q), element r <-> dW row base + 4q + r,
-  // column l15 of the fragment (16 lanes = one 64 B segment)
   auto flush = [&](int seg_end) {
-    // Derived from the segment end so that the flush addresses are formed
-    // here, not hoisted above the tile loop where they would cost registers.
-    float* const dwp = dw + (__builtin_amdgcn_readfirstlane(seg_end) - seg_end);
-#pragma unroll
-    for (int a = 0; a < RF; ++a) {
-      const int no = (wid * RF + a) * 16 + q * 4;
-#pragma unroll
-      for (int f = 0; f < NF; ++f) {
-        const int col = ct * (NF * 16) + f * 16 + l15;
-        if (col < Ki) {
-#pragma unroll
-          for (int r = 0; r < 4; ++r) atomicAdd(dwp + (int64_t)(no + r) * Ki + col, acc[a][f][r]);
-        }
-        acc[a][f] = floatx4{0.f, 0.f, 0.f, 0.f};
-      }
-      if (do_db && l15 == 0) {
-#pragma unroll
-        for (int r = 0; r < 4; ++r) atomicAdd(db + no + r, accb[a][r]);
-      }
-      accb[a] = floatx4{0.f, 0.f, 0.f, 0.f};
-    }
+    lwg_flush<RF, NF>(acc, accb, dw, db, Ki, ct, do_db, seg_end, wid, q, l15);
   };
 
-  // A block with LWG_SPLIT_TILES or more tiles flushes once half-way, after
-  // a multiple of three tiles so that the ring keeps its turn (the reason for
-  // the extra flush is in linear_wgrad.hip).
-  const int my_tiles = grp < nfull ? (nfull - grp + groups - 1) / groups : 0;
-  const int half = my_tiles >= LWG_SPLIT_TILES ? ((my_tiles + 1) / 2 + 2) / 3 * 3 : 0;
+  // the half-way flush comes after a multiple of three tiles, so the ring
+  // keeps its turn
+  const int my_tiles = lwg_my_tiles(grp, groups, nfull);
+  const int half = lwg_half_walk<3>(my_tiles);
   int end = half ? grp + half * groups : nfull;
   if (tile < nfull) {
     stage(zs0, xs0, tile);
@@ -295,6 +238,9 @@ __global__ __launch_bounds__(HB_THREADS, 1) void hidden_bwd_kernel(
       if (B % LWG_ROWS != 0 && nfull % groups == grp) {
         __syncthreads();  // the store above has read os0 if that was its tile
         const int64_t row0 = (int64_t)nfull * LWG_ROWS;
+        // written out, not ZI / XI::fill_tail: through the helpers this kernel's
+        // register count crosses an occupancy step
+        // (profiles/wgrad_family_refactor.md)
 #pragma unroll
         for (int j = 0; j < LWG_ROWS * ZSLOTS / HB_THREADS; ++j) {
           const int u = t + j * HB_THREADS;
@@ -332,8 +278,7 @@ __global__ __launch_bounds__(HB_THREADS, 1) void hidden_bwd_kernel(
 
 // 1 when the kernel can compute (No, Ki, B) at all
 extern "C" int hidden_bwd_can_run(int No, int Ki, int64_t B) {
-  return (No == 128 || No == 256) && Ki >= 8 && (Ki & 7) == 0 && Ki < (1 << 24) && B >= 1 &&
-         B < (1LL << 31) - LWG_ROWS;
+  return (No == 128 || No == 256) && lwg_bounds_ok(Ki, B);
 }
 
 // 1 when functional.py routes (No, Ki, B) here
@@ -350,38 +295,13 @@ extern "C" hipError_t launch_hidden_bwd(const bf16raw* dz, const bf16raw* x, con
                                         int Ki, int max_blocks, int num_cus, hipStream_t stream) {
   if (!hidden_bwd_can_run(No, Ki, B)) return hipErrorInvalidValue;
   if ((((uintptr_t)dz) | ((uintptr_t)x) | ((uintptr_t)dzin)) & 15) return hipErrorInvalidValue;
-  const int nf = lwg_nf(Ki);
-  const int ncol = (Ki + nf * 16 - 1) / (nf * 16);
-  const int ntiles = (int)((B + LWG_ROWS - 1) / LWG_ROWS);
   // one resident block per CU
-  int groups = (num_cus > 0 ? num_cus : 256) / ncol;
-  if (groups < 1) groups = 1;
-  // at least LWG_MIN_TILES tiles per block, as linear_wgrad_kernel
-  if (groups > ntiles / LWG_MIN_TILES) groups = ntiles / LWG_MIN_TILES;
-  if (groups < 1) groups = 1;
-  if (max_blocks > 0 && groups > max_blocks) groups = max_blocks;
-  int xcd_deal = 0;
-  if (groups >= 8) {
-    groups &= ~7;
-    xcd_deal = 1;
-  }
-  const dim3 grid(groups * ncol), block(HB_THREADS);
-#define HB_LAUNCH(RF, NF)                                                                  \
-  hidden_bwd_kernel<RF, NF><<<grid, block, 0, stream>>>(dz, x, w, dzin, dw, db, (int)B, Ki, \
-                                                        ncol, groups, xcd_deal)
-#define HB_LAUNCH_NF(RF) \
-  do {                   \
-    if (nf == 7)         \
-      HB_LAUNCH(RF, 7);  \
-    else                 \
-      HB_LAUNCH(RF, 8);  \
-  } while (0)
-  if (No == 128)
-    HB_LAUNCH_NF(1);
-  else
-    HB_LAUNCH_NF(2);
-#undef HB_LAUNCH_NF
-#undef HB_LAUNCH
+  const lwg_grid g = lwg_grid_plan(Ki, B, 1, max_blocks, num_cus);
+  lwg_dispatch<1, 2>(No / 128, g.nf, [&](auto rf, auto nf) {
+    hidden_bwd_kernel<decltype(rf)::value, decltype(nf)::value>
+        <<<g.groups * g.ncol, HB_THREADS, 0, stream>>>(dz, x, w, dzin, dw, db, (int)B, Ki, g.ncol,
+                                                       g.groups, g.xcd_deal);
+  });
   HIP_CHECK_LAUNCH();
   return hipSuccess;
 }

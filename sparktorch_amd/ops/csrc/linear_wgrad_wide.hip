@@ -27,13 +27,18 @@
 //     waves split the Ki columns; every wave reads all dz fragments;
 //   * every column tile produces the db of its own rows with a ones-fragment
 //     MFMA on the dz fragments of its image, fragment f in wave f % 4;
-//   * block ids are dealt so the column tiles of one row group share an XCD
-//     and start together: their x re-reads hit that XCD's L2.
+//   * the column tiles of one row group share an XCD: their x re-reads hit
+//     that XCD's L2.
 //
 // Rows past B: the (at most one) partial tile is staged through registers
 // with zero fill after the DMA loop over the full tiles.  Columns past No in
-// the last column tile are clamped to the row's last 16 B slot; their dW rows
-// and db entries are never flushed (MFMA output rows are independent).
+// the last column tile are clamped into the row; their dW rows and db entries
+// are never flushed.
+//
+// The images, the block deal, the walk's plan and the grid plan are
+// linear_wgrad_tile.h's.  The accumulate step and the flush are this file's
+// own: dW is held transposed to linear_wgrad.hip's and db is read in another
+// order.
 
 #include "linear_wgrad_tile.h"
 
@@ -48,12 +53,11 @@ __global__ __launch_bounds__(LWW_THREADS, 2) void linear_wgrad_wide_kernel(
   constexpr int KI = 64 * MF;
   constexpr int XSLOTS = KI / 8;                  // 16 B slots per x image row
   constexpr int ZSLOTS = LWG_XCOLS / 8;           // and per dz image row
-  constexpr int XCH = LWG_ROWS * KI * 2 / 1024;   // 1 KB DMA chunks per x tile
-  constexpr int ZCH = LWG_ROWS * LWG_XCOLS * 2 / 1024;
   constexpr int NB = (NF + 3) / 4;                // db fragments per wave
+  using ZI = lwg_slice_image<ZSLOTS, LWW_THREADS / 64>;  // dz: the block's column tile
+  using XI = lwg_row_image<XSLOTS, LWW_THREADS / 64>;    // x: whole rows
   static_assert(MF == 1 || MF == 2 || MF == 4, "Ki must be 64, 128 or 256");
   static_assert(NF >= 1 && NF * 16 <= LWG_XCOLS, "dz tile wider than its image");
-  static_assert(XCH % 4 == 0 && ZCH % 4 == 0, "DMA chunks are dealt evenly to the 4 waves");
 
   // One LDS variable per buffer, selected at compile time (the tile loop is
   // unrolled by two): the compiler can then tell the DMA into one pair from
@@ -68,49 +72,19 @@ __global__ __launch_bounds__(LWW_THREADS, 2) void linear_wgrad_wide_kernel(
   const int wid = __builtin_amdgcn_readfirstlane(t >> 6), lane = t & 63;
   const int l15 = lane & 15, q = lane >> 4;
 
-  // block id -> (row group, column tile).  Hardware deals consecutive ids
-  // round-robin over the 8 XCDs; with xcd_deal the ncol blocks of a group
-  // are consecutive slots of ONE XCD.
   int grp, ct;
-  if (xcd_deal) {
-    const int xcd = blockIdx.x & 7, j = blockIdx.x >> 3;
-    grp = (j / ncol) * 8 + xcd;
-    ct = j % ncol;
-  } else {
-    grp = blockIdx.x / ncol;
-    ct = blockIdx.x % ncol;
-  }
+  lwg_block_deal(ncol, xcd_deal, grp, ct);
   const int nfull = B / LWG_ROWS;   // full tiles: DMA, no bounds to check
   const int nslots = No >> 3;       // 16 B slots per dz row
   const int slot0 = ct * (NF * 2);  // first slot of this column tile
   const int row_base = ct * (NF * 16);  // and its first row of dW
 
-  // DMA source offsets.  Wave w issues chunks w, w + 4, ...: chunk c fills
-  // image rows c * RPC ... + RPC - 1, so a lane's row advances by a multiple
-  // of 8 from one of its chunks to the next, its swizzle key stays, and one
-  // 32-bit lane offset (plus a wave-uniform base) serves all of them.
-  constexpr int XRPC = 64 / XSLOTS, ZRPC = 64 / ZSLOTS;
-  static_assert(XCH == 4 || (4 * XRPC) % 8 == 0, "key must not depend on the chunk");
-  static_assert((4 * ZRPC) % 8 == 0, "key must not depend on the chunk");
-  const int xr0 = wid * XRPC + lane / XSLOTS;
-  const unsigned xoff = xr0 * KI + (((lane % XSLOTS) ^ lwg_key<XSLOTS>::key(xr0)) << 3);
-  const int zr0 = wid * ZRPC + lane / ZSLOTS;
-  int zgs = slot0 + ((lane % ZSLOTS) ^ lwg_key<ZSLOTS>::key(zr0));
-  if (zgs > nslots - 1) zgs = nslots - 1;
-  const unsigned zoff = (unsigned)zr0 * No + zgs * 8;
-
+  const unsigned xoff = XI::lane_off(wid, lane);
+  const unsigned zoff = ZI::lane_off(wid, lane, No, slot0, nslots);
   auto stage = [&](bf16raw* zn, bf16raw* xn, int tile) {
     const int64_t row0 = (int64_t)tile * LWG_ROWS;
-#pragma unroll
-    for (int i = 0; i < ZCH / 4; ++i) {
-      const bf16raw* g = dz + (row0 + i * 4 * ZRPC) * No;
-      mt_glds16(g + zoff, zn + (wid + 4 * i) * 512);
-    }
-#pragma unroll
-    for (int i = 0; i < XCH / 4; ++i) {
-      const bf16raw* g = x + (row0 + i * 4 * XRPC) * KI;
-      mt_glds16(g + xoff, xn + (wid + 4 * i) * 512);
-    }
+    ZI::dma(dz, zn, row0, zoff, wid, No);
+    XI::dma(x, xn, row0, xoff, wid);
   };
 
   mt_frag_t ones;
@@ -194,12 +168,9 @@ __global__ __launch_bounds__(LWW_THREADS, 2) void linear_wgrad_wide_kernel(
     }
   };
 
-  // A block with LWG_SPLIT_TILES or more tiles flushes once half-way (after
-  // an even count, so the buffer pairs keep their turn): fp32 rounding grows
-  // with the length and magnitude of one accumulator chain, and the extra
-  // flush halves both for the price of one more pass of atomics.
-  const int my_tiles = grp < nfull ? (nfull - grp + groups - 1) / groups : 0;
-  const int half = my_tiles >= LWG_SPLIT_TILES ? (((my_tiles + 1) / 2 + 1) & ~1) : 0;
+  // the half-way flush comes after an even count of tiles, so the buffer
+  // pairs keep their turn
+  const int half = lwg_half_walk<2>(lwg_my_tiles(grp, groups, nfull));
   int end = half ? grp + half * groups : nfull;
   if (tile < nfull) stage(zs0, xs0, tile);
   for (;;) {
@@ -214,25 +185,8 @@ __global__ __launch_bounds__(LWW_THREADS, 2) void linear_wgrad_wide_kernel(
     if (last && B % LWG_ROWS != 0 && nfull % groups == grp) {
       __syncthreads();
       const int64_t row0 = (int64_t)nfull * LWG_ROWS;
-#pragma unroll
-      for (int j = 0; j < LWG_ROWS * ZSLOTS / LWW_THREADS; ++j) {
-        const int u = t + j * LWW_THREADS;
-        const int row = u / ZSLOTS;
-        int gs = slot0 + ((u % ZSLOTS) ^ lwg_key<ZSLOTS>::key(row));
-        if (gs > nslots - 1) gs = nslots - 1;
-        shortx8 v = {};
-        if (row0 + row < B) v = *(const shortx8*)(dz + (row0 + row) * No + gs * 8);
-        *(shortx8*)(zs0 + u * 8) = v;
-      }
-#pragma unroll
-      for (int j = 0; j < MF; ++j) {
-        const int u = t + j * LWW_THREADS;
-        const int row = u / XSLOTS;
-        const int slot = (u % XSLOTS) ^ lwg_key<XSLOTS>::key(row);
-        shortx8 v = {};
-        if (row0 + row < B) v = *(const shortx8*)(x + (row0 + row) * KI + slot * 8);
-        *(shortx8*)(xs0 + u * 8) = v;
-      }
+      ZI::fill_tail(dz, zs0, row0, B, t, No, slot0, nslots);
+      XI::fill_tail(x, xs0, row0, B, t);
       __syncthreads();
       mma(zs0, xs0);
     }
@@ -250,8 +204,7 @@ __global__ __launch_bounds__(LWW_THREADS, 2) void linear_wgrad_wide_kernel(
 
 // 1 when the kernel can compute (No, Ki, B) at all
 extern "C" int linear_wgrad_wide_can_run(int No, int Ki, int64_t B) {
-  return (Ki == 64 || Ki == 128 || Ki == 256) && No >= 8 && (No & 7) == 0 && No < (1 << 24) &&
-         B >= 1 && B < (1LL << 31) - LWG_ROWS;
+  return (Ki == 64 || Ki == 128 || Ki == 256) && lwg_bounds_ok(No, B);
 }
 
 // 1 when linear_wgrad_into routes (No, Ki, B) here: layers that
@@ -268,40 +221,13 @@ extern "C" hipError_t launch_linear_wgrad_wide(const bf16raw* dz, const bf16raw*
                                                int max_blocks, int num_cus, hipStream_t stream) {
   if (!linear_wgrad_wide_can_run(No, Ki, B)) return hipErrorInvalidValue;
   if ((((uintptr_t)dz) | ((uintptr_t)x)) & 15) return hipErrorInvalidValue;
-  const int nf = lwg_nf(No);
-  const int ncol = (No + nf * 16 - 1) / (nf * 16);
-  const int ntiles = (int)((B + LWG_ROWS - 1) / LWG_ROWS);
   // two resident blocks per CU
-  int groups = 2 * (num_cus > 0 ? num_cus : 256) / ncol;
-  if (groups < 1) groups = 1;
-  // at least LWG_MIN_TILES tiles (512 rows, the split-K route's floor per
-  // slice) per block: fewer, longer register chains and fewer flushes
-  if (groups > ntiles / LWG_MIN_TILES) groups = ntiles / LWG_MIN_TILES;
-  if (groups < 1) groups = 1;
-  if (max_blocks > 0 && groups > max_blocks) groups = max_blocks;
-  int xcd_deal = 0;
-  if (groups >= 8) {
-    groups &= ~7;
-    xcd_deal = 1;
-  }
-  const dim3 grid(groups * ncol), block(LWW_THREADS);
-#define LWW_LAUNCH(MF, NF)                                                                      \
-  linear_wgrad_wide_kernel<MF, NF><<<grid, block, 0, stream>>>(dz, x, dw, db, (int)B, No, ncol, \
-                                                               groups, xcd_deal)
-#define LWW_LAUNCH_NF(MF) \
-  do {                    \
-    if (nf == 7)          \
-      LWW_LAUNCH(MF, 7);  \
-    else                  \
-      LWW_LAUNCH(MF, 8);  \
-  } while (0)
-  switch (Ki) {
-    case 64: LWW_LAUNCH_NF(1); break;
-    case 128: LWW_LAUNCH_NF(2); break;
-    default: LWW_LAUNCH_NF(4); break;
-  }
-#undef LWW_LAUNCH_NF
-#undef LWW_LAUNCH
+  const lwg_grid g = lwg_grid_plan(No, B, 2, max_blocks, num_cus);
+  lwg_dispatch<1, 2, 4>(Ki / 64, g.nf, [&](auto mf, auto nf) {
+    linear_wgrad_wide_kernel<decltype(mf)::value, decltype(nf)::value>
+        <<<g.groups * g.ncol, LWW_THREADS, 0, stream>>>(dz, x, dw, db, (int)B, No, g.ncol,
+                                                        g.groups, g.xcd_deal);
+  });
   HIP_CHECK_LAUNCH();
   return hipSuccess;
 }
