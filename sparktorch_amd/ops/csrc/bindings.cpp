@@ -9,128 +9,7 @@
 
 #include <cstdint>
 
-typedef uint16_t bf16raw;
-
-extern "C" {
-hipError_t launch_fused_adam(float*, const float*, float*, float*, int64_t, float, float, float,
-                             float, float, float, float, float, int, const int*, hipStream_t);
-hipError_t launch_increment_i32(int*, hipStream_t);
-hipError_t launch_fused_sgd(float*, const float*, float*, int64_t, float, float, float, float,
-                            float, int, int, int, hipStream_t);
-hipError_t launch_relu_bwd(const bf16raw*, const bf16raw*, bf16raw*, int64_t, hipStream_t);
-hipError_t launch_bias_grad(const bf16raw*, float*, int, int, float*, int,
-                            hipStream_t);
-hipError_t launch_small_wgrad(const bf16raw*, const bf16raw*, float*, float*, int, int64_t, int,
-                              int, hipStream_t);
-hipError_t launch_pad_nhwc(const bf16raw*, bf16raw*, int, int, int, int, int, hipStream_t);
-hipError_t launch_s2d_stem(const bf16raw*, bf16raw*, int, int, int, int, hipStream_t);
-hipError_t launch_flip_w2d(const bf16raw*, bf16raw*, int, int, int, hipStream_t);
-hipError_t launch_conv_implicit_fwd(const bf16raw*, const bf16raw*, const float*, bf16raw*, int,
-                                    int, int, int, int, int, int, int, int, int, int, int, int,
-                                    hipStream_t);
-hipError_t launch_conv_implicit_wgrad(const bf16raw*, const bf16raw*, float*, int, int, int, int,
-                                      int, int, int, int, int, int, float*, int, int,
-                                      hipStream_t);
-int conv_implicit_wgrad_slices(int, int);
-hipError_t launch_cast_f64_f32(const double*, float*, int64_t, hipStream_t);
-hipError_t launch_cast_f64_bf16(const double*, bf16raw*, int64_t, hipStream_t);
-hipError_t launch_cast_f32_bf16(const float*, bf16raw*, int64_t, hipStream_t);
-hipError_t launch_ce_fused(const bf16raw*, const int64_t*, float*, bf16raw*, int, int,
-                           hipStream_t);
-hipError_t launch_mse_fused(const bf16raw*, const bf16raw*, float*, bf16raw*, int64_t,
-                            hipStream_t);
-hipError_t launch_gemm_bf16(const void*, const void*, int, float*, bf16raw*, const float*, int,
-                            int, int, int64_t, int64_t, int64_t, int64_t, int, int, float*, int,
-                            hipStream_t);
-hipError_t launch_gemm_bf16_mask(const void*, const void*, int, float*, bf16raw*, const float*,
-                                 int, int, int, int64_t, int64_t, int64_t, int64_t, int, int,
-                                 float*, int, const bf16raw*, hipStream_t);
-int head_bwd_supported(int, int);
-int linear_wgrad_stream_supported(int, int, int64_t);
-int linear_wgrad_stream_can_run(int, int, int64_t);
-hipError_t launch_linear_wgrad_stream(const bf16raw*, const bf16raw*, float*, float*, int64_t, int,
-                                      int, int, int, hipStream_t);
-int linear_wgrad_wide_supported(int, int, int64_t);
-int linear_wgrad_wide_can_run(int, int, int64_t);
-hipError_t launch_linear_wgrad_wide(const bf16raw*, const bf16raw*, float*, float*, int64_t, int,
-                                    int, int, int, hipStream_t);
-int hidden_bwd_supported(int, int, int64_t);
-int hidden_bwd_can_run(int, int, int64_t);
-hipError_t launch_hidden_bwd(const bf16raw*, const bf16raw*, const bf16raw*, bf16raw*, float*,
-                             float*, int64_t, int, int, int, int, hipStream_t);
-int linear_fwd_stream_supported(int, int, int64_t);
-int64_t linear_fwd_stream_min_rows();
-int linear_fwd_stream_deep_supported(int, int, int64_t);
-int64_t linear_fwd_stream_deep_min_rows();
-hipError_t launch_linear_stream(const bf16raw*, const bf16raw*, bf16raw*, const float*,
-                                const bf16raw*, int64_t, int, int, int, int, int, int,
-                                hipStream_t);
-hipError_t launch_sample_gather(const void*, int, const void*, int, void*, void*, int*, const int*,
-                                uint32_t, int64_t, int, int, int, int, hipStream_t);
-hipError_t launch_head_bwd(const bf16raw*, const bf16raw*, const bf16raw*, bf16raw*, float*,
-                           float*, int, int, int, int, int, hipStream_t);
-hipError_t launch_head_ce(const bf16raw*, const float*, const bf16raw*, const int64_t*, bf16raw*,
-                          float*, float*, float*, bf16raw*, int, int, int, int, int, hipStream_t);
-hipError_t launch_head_mse(const bf16raw*, const float*, const bf16raw*, const bf16raw*, bf16raw*,
-                           float*, float*, float*, bf16raw*, int, int, int, int, int, hipStream_t);
-int hidden_head_ce_supported(int, int, int);
-int64_t hidden_head_ce_min_rows();
-hipError_t launch_hidden_head_ce(const bf16raw*, const bf16raw*, const float*, const bf16raw*,
-                                 const float*, const int64_t*, bf16raw*, float*, float*, float*,
-                                 bf16raw*, bf16raw*, int, int, int, int, int, int, hipStream_t);
-int linear_mse_supported(int, int);
-int linear_mse_chunk_cols(int);
-int64_t linear_mse_min_rows();
-hipError_t launch_linear_mse(const bf16raw*, const bf16raw*, const float*, const bf16raw*, bf16raw*,
-                             bf16raw*, float*, int, int, int, int, int, hipStream_t);
-int mlp_predict_supported(int, const int*, int, int, int64_t);
-int64_t mlp_predict_min_rows();
-hipError_t launch_mlp_predict(const bf16raw*, const bf16raw* const*, const float* const*,
-                              const int*, int, int, int, int64_t, int*, bf16raw*, int, int,
-                              hipStream_t);
-hipError_t launch_mlp_predict_f32(const float*, const bf16raw* const*, const float* const*,
-                                  const int*, int, int, int, int64_t, int*, bf16raw*, int, int,
-                                  hipStream_t);
-hipError_t launch_bn_stats(const bf16raw*, float*, float*, float*, float*, float*, float*, int,
-                           int, int64_t, float, float, int, hipStream_t);
-hipError_t launch_bn_apply(const bf16raw*, const bf16raw*, bf16raw*, const float*, const float*,
-                           const float*, const float*, int, int64_t, int64_t, int, hipStream_t);
-hipError_t launch_bn_bwd_reduce(const bf16raw*, const bf16raw*, const bf16raw*, const float*,
-                                const float*, float*, float*, int, int, int64_t, int,
-                                hipStream_t);
-hipError_t launch_bn_bwd_dx(const bf16raw*, const bf16raw*, const bf16raw*, const float*,
-                            const float*, const float*, const float*, const float*, bf16raw*,
-                            int, int64_t, int64_t, float, int, hipStream_t);
-hipError_t launch_add_relu(const bf16raw*, const bf16raw*, bf16raw*, int64_t, hipStream_t);
-hipError_t launch_maxpool_gen_fwd(const bf16raw*, bf16raw*, uint8_t*, int64_t, int, int, int,
-                                  int, int, int, int, hipStream_t);
-hipError_t launch_maxpool_gen_bwd(const bf16raw*, const uint8_t*, bf16raw*, int64_t, int, int,
-                                  int, int, int, int, int, hipStream_t);
-hipError_t launch_gap_fwd(const bf16raw*, bf16raw*, int64_t, int64_t, hipStream_t);
-hipError_t launch_gap_bwd(const bf16raw*, bf16raw*, int64_t, int64_t, hipStream_t);
-hipError_t launch_im2col_nhwc(const bf16raw*, bf16raw*, int, int, int, int, int, int, int, int,
-                              int, int, int, int, int, hipStream_t);
-hipError_t launch_col2im_nhwc(const bf16raw*, bf16raw*, int, int, int, int, int, int, int, int,
-                              int, int, int, int, int, hipStream_t);
-hipError_t launch_maxpool_nhwc_fwd(const bf16raw*, bf16raw*, uint8_t*, int, int, int, int, int,
-                                   int, int, int, int, hipStream_t);
-hipError_t launch_maxpool_nhwc_bwd(const bf16raw*, const uint8_t*, bf16raw*, int, int, int, int,
-                                   int, int, int, int, int, hipStream_t);
-hipError_t launch_gap_nhwc_fwd(const bf16raw*, bf16raw*, int, int, int64_t, hipStream_t);
-hipError_t launch_gap_nhwc_bwd(const bf16raw*, bf16raw*, int, int, int64_t, hipStream_t);
-hipError_t launch_bn_stats_nhwc(const bf16raw*, float*, float*, float*, float*, float*, float*,
-                                int64_t, int, float, float, int, float*, int, hipStream_t);
-hipError_t launch_bn_apply_nhwc(const bf16raw*, const bf16raw*, bf16raw*, const float*,
-                                const float*, const float*, const float*, int, int64_t, int,
-                                hipStream_t);
-hipError_t launch_bn_bwd_reduce_nhwc(const bf16raw*, const bf16raw*, const bf16raw*,
-                                     const float*, const float*, const float*, const float*,
-                                     float*, float*, int64_t, int, int, float*, int,
-                                     hipStream_t);
-hipError_t launch_bn_bwd_dx_nhwc(const bf16raw*, const bf16raw*, const bf16raw*, const float*,
-                                 const float*, const float*, const float*, const float*,
-                                 const float*, bf16raw*, int, int64_t, float, int, hipStream_t);
-}
+#include "launchers.h"
 
 #define CHECK_HIP(err)                                                              \
   TORCH_CHECK((err) == hipSuccess, "HIP kernel launch failed: ", hipGetErrorString(err))
@@ -144,6 +23,21 @@ static void check_gpu_contig(const at::Tensor& t, c10::ScalarType dt, const char
   TORCH_CHECK(t.is_contiguous(), name, " must be contiguous");
   TORCH_CHECK(t.scalar_type() == dt, name, " has wrong dtype");
 }
+
+// An optional fp32 vector of n elements (a bias, a db): its pointer, null
+// when it is absent.
+static float* opt_f32_vec(const c10::optional<at::Tensor>& t, int64_t n, const char* name) {
+  if (!t.has_value()) return nullptr;
+  check_gpu_contig(*t, at::kFloat, name);
+  TORCH_CHECK(t->numel() == n, name, " must have ", n, " elements");
+  return t->data_ptr<float>();
+}
+
+static bool aligned16(const at::Tensor& t) { return (((uintptr_t)t.data_ptr()) & 15) == 0; }
+
+// the raw bits of a bf16 tensor, to read and to write
+static const bf16raw* bf16_in(const at::Tensor& t) { return (const bf16raw*)t.data_ptr(); }
+static bf16raw* bf16_out(const at::Tensor& t) { return (bf16raw*)t.data_ptr(); }
 
 // ---------------------------------------------------------------------------
 
@@ -181,8 +75,8 @@ at::Tensor relu_bwd(at::Tensor dy, at::Tensor y) {
   check_gpu_contig(dy, at::kBFloat16, "dy");
   check_gpu_contig(y, at::kBFloat16, "y");
   auto dz = at::empty_like(dy);
-  CHECK_HIP(launch_relu_bwd((const bf16raw*)dy.data_ptr(), (const bf16raw*)y.data_ptr(),
-                            (bf16raw*)dz.data_ptr(), dy.numel(), cur_stream()));
+  CHECK_HIP(launch_relu_bwd(bf16_in(dy), bf16_in(y),
+                            bf16_out(dz), dy.numel(), cur_stream()));
   return dz;
 }
 
@@ -210,7 +104,7 @@ at::Tensor bias_grad(at::Tensor dz) {
     scratch = at::empty({(int64_t)S * N}, dz.options().dtype(at::kFloat));
     sp = scratch.data_ptr<float>();
   }
-  CHECK_HIP(launch_bias_grad((const bf16raw*)dz.data_ptr(), db.data_ptr<float>(), (int)M, N, sp,
+  CHECK_HIP(launch_bias_grad(bf16_in(dz), db.data_ptr<float>(), (int)M, N, sp,
                              S, cur_stream()));
   return db;
 }
@@ -222,7 +116,7 @@ at::Tensor pad_nhwc(at::Tensor x, int64_t P) {
   TORCH_CHECK(x.dim() == 4 && x.size(3) % 8 == 0, "pad_nhwc wants [B,H,W,C], C%8==0");
   int B = (int)x.size(0), H = (int)x.size(1), W = (int)x.size(2), C = (int)x.size(3);
   auto xP = at::empty({B, H + 2 * P, W + 2 * P, C}, x.options());
-  CHECK_HIP(launch_pad_nhwc((const bf16raw*)x.data_ptr(), (bf16raw*)xP.data_ptr(), B, H, W, C,
+  CHECK_HIP(launch_pad_nhwc(bf16_in(x), bf16_out(xP), B, H, W, C,
                             (int)P, cur_stream()));
   return xP;
 }
@@ -233,7 +127,7 @@ at::Tensor s2d_stem(at::Tensor x, int64_t P) {
               "s2d_stem wants [B, even H, even W, 3]");
   int B = (int)x.size(0), H = (int)x.size(1), W = (int)x.size(2);
   auto out = at::empty({B, H / 2 + 2 * P, W / 2 + 2 * P, 16}, x.options());
-  CHECK_HIP(launch_s2d_stem((const bf16raw*)x.data_ptr(), (bf16raw*)out.data_ptr(), B, H, W,
+  CHECK_HIP(launch_s2d_stem(bf16_in(x), bf16_out(out), B, H, W,
                             (int)P, cur_stream()));
   return out;
 }
@@ -243,7 +137,7 @@ at::Tensor flip_w2d(at::Tensor w2d, int64_t CI, int64_t KHW) {
   TORCH_CHECK(w2d.dim() == 2 && w2d.size(1) == KHW * CI, "w2d must be [CO, KH*KW*CI]");
   int CO = (int)w2d.size(0);
   auto wf = at::empty({CI, KHW * CO}, w2d.options());
-  CHECK_HIP(launch_flip_w2d((const bf16raw*)w2d.data_ptr(), (bf16raw*)wf.data_ptr(), CO, (int)CI,
+  CHECK_HIP(launch_flip_w2d(bf16_in(w2d), bf16_out(wf), CO, (int)CI,
                             (int)KHW, cur_stream()));
   return wf;
 }
@@ -268,8 +162,8 @@ at::Tensor conv_implicit_fwd(at::Tensor xP, at::Tensor wmat, c10::optional<at::T
     check_gpu_contig(*bias, at::kFloat, "bias");
     bp = bias->data_ptr<float>();
   }
-  CHECK_HIP(launch_conv_implicit_fwd((const bf16raw*)xP.data_ptr(),
-                                     (const bf16raw*)wmat.data_ptr(), bp, (bf16raw*)y.data_ptr(),
+  CHECK_HIP(launch_conv_implicit_fwd(bf16_in(xP),
+                                     bf16_in(wmat), bp, bf16_out(y),
                                      B, Hp, Wp, CI, (int)KH, (int)KW, (int)SH, (int)SW, N, Kpad,
                                      relu ? 1 : 0, (int)OHo, (int)OWo, cur_stream()));
   return y;
@@ -297,8 +191,8 @@ at::Tensor conv_implicit_wgrad(at::Tensor dz, at::Tensor xP, int64_t KH, int64_t
     ws = at::empty({zs, CO, N}, dw.options());
     wsp = ws.data_ptr<float>();
   }
-  CHECK_HIP(launch_conv_implicit_wgrad((const bf16raw*)dz.data_ptr(),
-                                       (const bf16raw*)xP.data_ptr(), dw.data_ptr<float>(), CO,
+  CHECK_HIP(launch_conv_implicit_wgrad(bf16_in(dz),
+                                       bf16_in(xP), dw.data_ptr<float>(), CO,
                                        B, Hp, Wp, CI, (int)KH, (int)KW, (int)SH, (int)SW,
                                        (int)splitk, wsp, (int)OHo, (int)OWo, cur_stream()));
   return dw;
@@ -315,7 +209,7 @@ at::Tensor cast_f64_f32(at::Tensor src) {
 at::Tensor cast_f64_bf16(at::Tensor src) {
   check_gpu_contig(src, at::kDouble, "src");
   auto dst = at::empty(src.sizes(), src.options().dtype(at::kBFloat16));
-  CHECK_HIP(launch_cast_f64_bf16(src.data_ptr<double>(), (bf16raw*)dst.data_ptr(), src.numel(),
+  CHECK_HIP(launch_cast_f64_bf16(src.data_ptr<double>(), bf16_out(dst), src.numel(),
                                  cur_stream()));
   return dst;
 }
@@ -323,7 +217,7 @@ at::Tensor cast_f64_bf16(at::Tensor src) {
 at::Tensor cast_f32_bf16(at::Tensor src) {
   check_gpu_contig(src, at::kFloat, "src");
   auto dst = at::empty(src.sizes(), src.options().dtype(at::kBFloat16));
-  CHECK_HIP(launch_cast_f32_bf16(src.data_ptr<float>(), (bf16raw*)dst.data_ptr(), src.numel(),
+  CHECK_HIP(launch_cast_f32_bf16(src.data_ptr<float>(), bf16_out(dst), src.numel(),
                                  cur_stream()));
   return dst;
 }
@@ -334,8 +228,8 @@ std::tuple<at::Tensor, at::Tensor> ce_fused(at::Tensor logits, at::Tensor target
   TORCH_CHECK(logits.dim() == 2);
   auto loss = at::zeros({}, logits.options().dtype(at::kFloat));
   auto dlogits = at::empty_like(logits);
-  CHECK_HIP(launch_ce_fused((const bf16raw*)logits.data_ptr(), targets.data_ptr<int64_t>(),
-                            loss.data_ptr<float>(), (bf16raw*)dlogits.data_ptr(),
+  CHECK_HIP(launch_ce_fused(bf16_in(logits), targets.data_ptr<int64_t>(),
+                            loss.data_ptr<float>(), bf16_out(dlogits),
                             (int)logits.size(0), (int)logits.size(1), cur_stream()));
   return {loss, dlogits};
 }
@@ -345,8 +239,8 @@ std::tuple<at::Tensor, at::Tensor> mse_fused(at::Tensor pred, at::Tensor target)
   check_gpu_contig(target, at::kBFloat16, "target");
   auto loss = at::zeros({}, pred.options().dtype(at::kFloat));
   auto dpred = at::empty_like(pred);
-  CHECK_HIP(launch_mse_fused((const bf16raw*)pred.data_ptr(), (const bf16raw*)target.data_ptr(),
-                             loss.data_ptr<float>(), (bf16raw*)dpred.data_ptr(), pred.numel(),
+  CHECK_HIP(launch_mse_fused(bf16_in(pred), bf16_in(target),
+                             loss.data_ptr<float>(), bf16_out(dpred), pred.numel(),
                              cur_stream()));
   return {loss, dpred};
 }
@@ -360,51 +254,53 @@ std::tuple<at::Tensor, at::Tensor> mse_fused(at::Tensor pred, at::Tensor target)
 // stream_route adds what the public bindings ask before they take it: a big
 // enough M and 16-byte aligned operands.  Forward and both dgrads share it,
 // so one shape always takes one route.
-bool linear_fwd_stream_ok(int64_t n_out, int64_t k_red, int64_t M) {
-  return n_out <= 256 && k_red < (1 << 24) &&
-         linear_fwd_stream_supported((int)n_out, (int)k_red, M) != 0;
+
+// A kernel file's (n_out, k_red, rows) shape predicate behind the range of its
+// launcher's int arguments: `fits` bounds the two widths before they are
+// narrowed.  The streaming kernels hold a full row of <= 256 outputs; the
+// wide-layer wgrad holds a <= 256-wide input instead.
+static bool narrow_fits(int64_t n_out, int64_t k_red) { return n_out <= 256 && k_red < (1 << 24); }
+static bool wide_fits(int64_t n_out, int64_t k_red) { return n_out < (1 << 24) && k_red <= 256; }
+
+template <bool (*fits)(int64_t, int64_t), int (*pred)(int, int, int64_t)>
+static bool shape_pred(int64_t n_out, int64_t k_red, int64_t rows) {
+  return fits(n_out, k_red) && pred((int)n_out, (int)k_red, rows) != 0;
 }
 
-static bool aligned16(const at::Tensor& t) { return (((uintptr_t)t.data_ptr()) & 15) == 0; }
+constexpr auto linear_fwd_stream_ok = shape_pred<narrow_fits, linear_fwd_stream_supported>;
+constexpr auto linear_fwd_stream_deep_ok =
+    shape_pred<narrow_fits, linear_fwd_stream_deep_supported>;
 
-// Routing threshold: the measured one of linear_stream.hip unless a test has
-// set another (set_linear_stream_min_rows; negative = back to the measured).
-static int64_t g_stream_min_rows = -1;
+// A routing threshold: the kernel file's measured one unless a test has set
+// another (negative = back to the measured; set returns the old setting).
+template <int64_t (*measured)()>
+struct MinRows {
+  static int64_t& setting() {
+    static int64_t rows = -1;
+    return rows;
+  }
+  static int64_t get() { return setting() >= 0 ? setting() : measured(); }
+  static int64_t set(int64_t rows) {
+    const int64_t old = setting();
+    setting() = rows;
+    return old;
+  }
+};
+// rows from which a supported shape is routed to linear_stream.hip, and from
+// which a routed K > 256 forward takes its deep-K kernel
+using StreamMinRows = MinRows<linear_fwd_stream_min_rows>;
+using StreamDeepMinRows = MinRows<linear_fwd_stream_deep_min_rows>;
 
-int64_t linear_stream_min_rows() {
-  return g_stream_min_rows >= 0 ? g_stream_min_rows : linear_fwd_stream_min_rows();
-}
-
-int64_t set_linear_stream_min_rows(int64_t rows) {
-  const int64_t old = g_stream_min_rows;
-  g_stream_min_rows = rows;
-  return old;
-}
-
-// The same for the row threshold between linear_stream.hip's two forwards.
-static int64_t g_stream_deep_min_rows = -1;
-
-int64_t linear_stream_deep_min_rows() {
-  return g_stream_deep_min_rows >= 0 ? g_stream_deep_min_rows : linear_fwd_stream_deep_min_rows();
-}
-
-int64_t set_linear_stream_deep_min_rows(int64_t rows) {
-  const int64_t old = g_stream_deep_min_rows;
-  g_stream_deep_min_rows = rows;
-  return old;
-}
-
-// launch_linear_stream's fwd_path for a routed forward: 2 = the deep-K
-// kernel, 1 = the 128-row kernel
+// launch_linear_stream's fwd_path for a routed forward
 static int stream_fwd_path(int64_t N, int64_t K, int64_t M) {
-  return M >= linear_stream_deep_min_rows() && linear_fwd_stream_deep_supported((int)N, (int)K, M)
-             ? 2
-             : 1;
+  return M >= StreamDeepMinRows::get() && linear_fwd_stream_deep_supported((int)N, (int)K, M)
+             ? LS_PATH_DEEP
+             : LS_PATH_TILE128;
 }
 
 static bool stream_route(const at::Tensor& a, const at::Tensor& w, int64_t n_out, int64_t k_red,
                          int64_t M) {
-  return w.scalar_type() == at::kBFloat16 && M >= linear_stream_min_rows() &&
+  return w.scalar_type() == at::kBFloat16 && M >= StreamMinRows::get() &&
          linear_fwd_stream_ok(n_out, k_red, M) && aligned16(a) && aligned16(w);
 }
 
@@ -413,9 +309,9 @@ static int fwd_epi(const c10::optional<at::Tensor>& bias, bool relu, const float
   if (bias.has_value()) {
     check_gpu_contig(*bias, at::kFloat, "bias");
     *bptr = bias->data_ptr<float>();
-    return relu ? 3 : 2;  // EPI_BIAS_RELU : EPI_BIAS
+    return relu ? EPI_BIAS_RELU : EPI_BIAS;
   }
-  return relu ? 4 : 1;  // EPI_RELU : EPI_BF16
+  return relu ? EPI_RELU : EPI_BF16;
 }
 
 // allow_stream = false pins the call to gemm.hip's tiles (the conv col
@@ -431,14 +327,15 @@ at::Tensor linear_fwd(at::Tensor x, at::Tensor w, c10::optional<at::Tensor> bias
   const float* bptr = nullptr;
   const int epi = fwd_epi(bias, relu, &bptr);
   if (allow_stream && stream_route(x, w, N, K, M)) {
-    CHECK_HIP(launch_linear_stream((const bf16raw*)x.data_ptr(), (const bf16raw*)w.data_ptr(),
-                                   (bf16raw*)y.data_ptr(), bptr, nullptr, M, (int)N, (int)K, epi,
-                                   /*b_kn*/ 0, 0, stream_fwd_path(N, K, M), cur_stream()));
+    CHECK_HIP(launch_linear_stream(bf16_in(x), bf16_in(w), bf16_out(y), bptr, nullptr, M, (int)N,
+                                   (int)K, epi, /*b_kn*/ 0, 0, stream_fwd_path(N, K, M),
+                                   cur_stream()));
     return y;
   }
   CHECK_HIP(launch_gemm_bf16(x.data_ptr(), w.data_ptr(), w.scalar_type() == at::kFloat ? 1 : 0,
-                             nullptr, (bf16raw*)y.data_ptr(), bptr, (int)M, (int)N, (int)K,
-                             /*sam*/ K, /*sak*/ 1, /*sbk*/ 1, /*sbn*/ K, epi, 1, nullptr, -1, cur_stream()));
+                             nullptr, bf16_out(y), bptr, (int)M, (int)N, (int)K,
+                             /*sam*/ K, /*sak*/ 1, /*sbk*/ 1, /*sbn*/ K, epi, 1, nullptr, -1,
+                             cur_stream()));
   return y;
 }
 
@@ -454,16 +351,16 @@ at::Tensor linear_fwd_stream(at::Tensor x, at::Tensor w, c10::optional<at::Tenso
   int64_t M = x.size(0), K = x.size(1), N = w.size(0);
   TORCH_CHECK(linear_fwd_stream_ok(N, K, M), "linear_fwd_stream: unsupported (N, K, M)");
   TORCH_CHECK(aligned16(x) && aligned16(w), "linear_fwd_stream wants 16-byte aligned x and w");
-  TORCH_CHECK(path >= 0 && path <= 2, "linear_fwd_stream: path is 0 (automatic), 1 or 2");
-  TORCH_CHECK(path != 2 || linear_fwd_stream_deep_supported((int)N, (int)K, M) != 0,
+  TORCH_CHECK(path >= LS_PATH_AUTO && path <= LS_PATH_DEEP,
+              "linear_fwd_stream: path is 0 (automatic), 1 or 2");
+  TORCH_CHECK(path != LS_PATH_DEEP || linear_fwd_stream_deep_supported((int)N, (int)K, M) != 0,
               "linear_fwd_stream: the deep-K kernel wants K > 256");
-  if (path == 0) path = stream_fwd_path(N, K, M);
+  if (path == LS_PATH_AUTO) path = stream_fwd_path(N, K, M);
   auto y = at::empty({M, N}, x.options());
   const float* bptr = nullptr;
   const int epi = fwd_epi(bias, relu, &bptr);
-  CHECK_HIP(launch_linear_stream((const bf16raw*)x.data_ptr(), (const bf16raw*)w.data_ptr(),
-                                 (bf16raw*)y.data_ptr(), bptr, nullptr, M, (int)N, (int)K, epi, 0,
-                                 0, (int)path, cur_stream()));
+  CHECK_HIP(launch_linear_stream(bf16_in(x), bf16_in(w), bf16_out(y), bptr, nullptr, M, (int)N,
+                                 (int)K, epi, /*b_kn*/ 0, 0, (int)path, cur_stream()));
   return y;
 }
 
@@ -474,14 +371,15 @@ at::Tensor linear_dgrad(at::Tensor dz, at::Tensor w, bool allow_stream) {
   TORCH_CHECK(w.size(0) == N, "shape mismatch");
   auto dx = at::empty({M, K}, dz.options());
   if (allow_stream && stream_route(dz, w, K, N, M)) {
-    CHECK_HIP(launch_linear_stream((const bf16raw*)dz.data_ptr(), (const bf16raw*)w.data_ptr(),
-                                   (bf16raw*)dx.data_ptr(), nullptr, nullptr, M, (int)K, (int)N,
-                                   /*EPI_BF16*/ 1, /*b_kn*/ 1, 0, 0, cur_stream()));
+    CHECK_HIP(launch_linear_stream(bf16_in(dz), bf16_in(w), bf16_out(dx), nullptr, nullptr, M,
+                                   (int)K, (int)N, EPI_BF16, /*b_kn*/ 1, 0, LS_PATH_AUTO,
+                                   cur_stream()));
     return dx;
   }
   CHECK_HIP(launch_gemm_bf16(dz.data_ptr(), w.data_ptr(), w.scalar_type() == at::kFloat ? 1 : 0,
-                             nullptr, (bf16raw*)dx.data_ptr(), nullptr, (int)M, (int)K, (int)N,
-                             /*sam*/ N, /*sak*/ 1, /*sbk*/ K, /*sbn*/ 1, 1, 1, nullptr, -1, cur_stream()));
+                             nullptr, bf16_out(dx), nullptr, (int)M, (int)K, (int)N,
+                             /*sam*/ N, /*sak*/ 1, /*sbk*/ K, /*sbn*/ 1, EPI_BF16, 1, nullptr, -1,
+                             cur_stream()));
   return dx;
 }
 
@@ -498,17 +396,16 @@ at::Tensor linear_dgrad_relu(at::Tensor dz, at::Tensor w, at::Tensor y_prev, boo
               "y_prev must be [M, K_in]");
   auto dx = at::empty({M, K}, dz.options());
   if (allow_stream && stream_route(dz, w, K, N, M) && aligned16(y_prev)) {
-    CHECK_HIP(launch_linear_stream((const bf16raw*)dz.data_ptr(), (const bf16raw*)w.data_ptr(),
-                                   (bf16raw*)dx.data_ptr(), nullptr,
-                                   (const bf16raw*)y_prev.data_ptr(), M, (int)K, (int)N,
-                                   /*EPI_BF16_MASK*/ 6, /*b_kn*/ 1, 0, 0, cur_stream()));
+    CHECK_HIP(launch_linear_stream(bf16_in(dz), bf16_in(w), bf16_out(dx), nullptr,
+                                   bf16_in(y_prev), M, (int)K, (int)N, EPI_BF16_MASK, /*b_kn*/ 1,
+                                   0, LS_PATH_AUTO, cur_stream()));
     return dx;
   }
   CHECK_HIP(launch_gemm_bf16_mask(dz.data_ptr(), w.data_ptr(),
                                   w.scalar_type() == at::kFloat ? 1 : 0, nullptr,
-                                  (bf16raw*)dx.data_ptr(), nullptr, (int)M, (int)K, (int)N,
-                                  /*sam*/ N, /*sak*/ 1, /*sbk*/ K, /*sbn*/ 1, 6, 1, nullptr, -1,
-                                  (const bf16raw*)y_prev.data_ptr(), cur_stream()));
+                                  bf16_out(dx), nullptr, (int)M, (int)K, (int)N,
+                                  /*sam*/ N, /*sak*/ 1, /*sbk*/ K, /*sbn*/ 1, EPI_BF16_MASK, 1,
+                                  nullptr, -1, bf16_in(y_prev), cur_stream()));
   return dx;
 }
 
@@ -526,12 +423,12 @@ at::Tensor linear_dgrad_stream(at::Tensor dz, at::Tensor w, c10::optional<at::Te
     TORCH_CHECK(y_prev->dim() == 2 && y_prev->size(0) == M && y_prev->size(1) == K,
                 "y_prev must be [M, K_in]");
     TORCH_CHECK(aligned16(*y_prev), "linear_dgrad_stream wants a 16-byte aligned y_prev");
-    mptr = (const bf16raw*)y_prev->data_ptr();
+    mptr = bf16_in(*y_prev);
   }
   auto dx = at::empty({M, K}, dz.options());
-  CHECK_HIP(launch_linear_stream((const bf16raw*)dz.data_ptr(), (const bf16raw*)w.data_ptr(),
-                                 (bf16raw*)dx.data_ptr(), nullptr, mptr, M, (int)K, (int)N,
-                                 mptr ? 6 : 1, /*b_kn*/ 1, 0, 0, cur_stream()));
+  CHECK_HIP(launch_linear_stream(bf16_in(dz), bf16_in(w), bf16_out(dx), nullptr, mptr, M, (int)K,
+                                 (int)N, mptr ? EPI_BF16_MASK : EPI_BF16, /*b_kn*/ 1, 0,
+                                 LS_PATH_AUTO, cur_stream()));
   return dx;
 }
 
@@ -615,103 +512,69 @@ at::Tensor linear_head_bwd(at::Tensor dz_out, at::Tensor w, at::Tensor y_in, at:
                   y_in.size(1) == H && dw.size(0) == C && dw.size(1) == H,
               "shape mismatch");
   TORCH_CHECK(head_bwd_ok(C, H), "linear_head_bwd: unsupported (C, H); use the per-layer route");
-  float* dbp = nullptr;
-  if (db.has_value()) {
-    check_gpu_contig(*db, at::kFloat, "db");
-    TORCH_CHECK(db->numel() == C);
-    dbp = db->data_ptr<float>();
-  }
+  float* dbp = opt_f32_vec(db, C, "db");
   auto dz_in = at::empty({B, H}, y_in.options());
-  TORCH_CHECK(((uintptr_t)y_in.data_ptr() & 15) == 0 && ((uintptr_t)dz_in.data_ptr() & 15) == 0,
+  TORCH_CHECK(aligned16(y_in) && aligned16(dz_in),
               "linear_head_bwd wants 16-byte aligned activations");
-  CHECK_HIP(launch_head_bwd((const bf16raw*)dz_out.data_ptr(), (const bf16raw*)w.data_ptr(),
-                            (const bf16raw*)y_in.data_ptr(), (bf16raw*)dz_in.data_ptr(),
+  CHECK_HIP(launch_head_bwd(bf16_in(dz_out), bf16_in(w), bf16_in(y_in), bf16_out(dz_in),
                             dw.data_ptr<float>(), dbp, (int)B, (int)C, (int)H, (int)max_blocks,
                             head_num_cus(), cur_stream()));
   return dz_in;
 }
 
-// Head forward + mean cross-entropy + head backward in one pass over y_in
-// (head_bwd.hip, head_ce_kernel): returns (loss, dz_in, logits or an empty
-// tensor); dw / db are accumulated into, the loss is defined by the call.
+// Head forward + loss + head backward in one pass over y_in (head_bwd.hip):
+// returns (loss, dz_in, the head's output or an empty tensor); dw / db are
+// accumulated into, the loss is defined by the call.  The two losses differ in
+// the target they read (its element type TgtT, dtype and rank) and the
+// launcher.
+template <typename TgtT>
+static std::tuple<at::Tensor, at::Tensor, at::Tensor> head_loss(
+    const char* name, c10::ScalarType tgt_dtype, int64_t tgt_rank,
+    hipError_t (*launch)(const bf16raw*, const float*, const bf16raw*, const TgtT*, bf16raw*,
+                         float*, float*, float*, bf16raw*, int, int, int, int, int, hipStream_t),
+    const at::Tensor& y_in, const at::Tensor& w, const c10::optional<at::Tensor>& bias,
+    const at::Tensor& target, const at::Tensor& dw, const c10::optional<at::Tensor>& db,
+    bool want_out, int64_t max_blocks) {
+  check_gpu_contig(y_in, at::kBFloat16, "y_in");
+  check_gpu_contig(w, at::kBFloat16, "w");
+  check_gpu_contig(target, tgt_dtype, "target");
+  check_gpu_contig(dw, at::kFloat, "dw");
+  TORCH_CHECK(y_in.dim() == 2 && w.dim() == 2 && target.dim() == tgt_rank);
+  int64_t B = y_in.size(0), H = y_in.size(1), C = w.size(0);
+  TORCH_CHECK(B >= 1 && B < (1LL << 31) && w.size(1) == H && target.size(0) == B &&
+                  (tgt_rank == 1 || target.size(1) == C) && dw.dim() == 2 && dw.size(0) == C &&
+                  dw.size(1) == H,
+              "shape mismatch");
+  TORCH_CHECK(head_bwd_ok(C, H), name, ": unsupported (C, H); use the three-step route");
+  const float* bp = opt_f32_vec(bias, C, "bias");
+  float* dbp = opt_f32_vec(db, C, "db");
+  auto loss = at::empty({}, y_in.options().dtype(at::kFloat));
+  auto dz_in = at::empty({B, H}, y_in.options());
+  auto out = want_out ? at::empty({B, C}, y_in.options()) : at::empty({0}, y_in.options());
+  TORCH_CHECK(aligned16(y_in) && aligned16(dz_in) && aligned16(w), name,
+              " wants 16-byte aligned activations and weights");
+  CHECK_HIP(launch(bf16_in(w), bp, bf16_in(y_in), (const TgtT*)target.data_ptr(), bf16_out(dz_in),
+                   dw.data_ptr<float>(), dbp, loss.data_ptr<float>(),
+                   want_out ? bf16_out(out) : nullptr, (int)B, (int)C, (int)H, (int)max_blocks,
+                   head_num_cus(), cur_stream()));
+  return {loss, dz_in, out};
+}
+
+// mean cross-entropy against int64 [B] class ids (head_ce_kernel)
 std::tuple<at::Tensor, at::Tensor, at::Tensor> linear_head_ce(
     at::Tensor y_in, at::Tensor w, c10::optional<at::Tensor> bias, at::Tensor target,
     at::Tensor dw, c10::optional<at::Tensor> db, bool want_logits, int64_t max_blocks) {
-  check_gpu_contig(y_in, at::kBFloat16, "y_in");
-  check_gpu_contig(w, at::kBFloat16, "w");
-  check_gpu_contig(target, at::kLong, "target");
-  check_gpu_contig(dw, at::kFloat, "dw");
-  TORCH_CHECK(y_in.dim() == 2 && w.dim() == 2 && target.dim() == 1);
-  int64_t B = y_in.size(0), H = y_in.size(1), C = w.size(0);
-  TORCH_CHECK(B >= 1 && B < (1LL << 31) && w.size(1) == H && target.size(0) == B &&
-                  dw.dim() == 2 && dw.size(0) == C && dw.size(1) == H,
-              "shape mismatch");
-  TORCH_CHECK(head_bwd_ok(C, H), "linear_head_ce: unsupported (C, H); use the three-step route");
-  const float* bp = nullptr;
-  if (bias.has_value()) {
-    check_gpu_contig(*bias, at::kFloat, "bias");
-    TORCH_CHECK(bias->numel() == C);
-    bp = bias->data_ptr<float>();
-  }
-  float* dbp = nullptr;
-  if (db.has_value()) {
-    check_gpu_contig(*db, at::kFloat, "db");
-    TORCH_CHECK(db->numel() == C);
-    dbp = db->data_ptr<float>();
-  }
-  auto loss = at::empty({}, y_in.options().dtype(at::kFloat));
-  auto dz_in = at::empty({B, H}, y_in.options());
-  auto logits = want_logits ? at::empty({B, C}, y_in.options()) : at::empty({0}, y_in.options());
-  TORCH_CHECK(((uintptr_t)y_in.data_ptr() & 15) == 0 && ((uintptr_t)dz_in.data_ptr() & 15) == 0 &&
-                  ((uintptr_t)w.data_ptr() & 15) == 0,
-              "linear_head_ce wants 16-byte aligned activations and weights");
-  CHECK_HIP(launch_head_ce((const bf16raw*)w.data_ptr(), bp, (const bf16raw*)y_in.data_ptr(),
-                           target.data_ptr<int64_t>(), (bf16raw*)dz_in.data_ptr(),
-                           dw.data_ptr<float>(), dbp, loss.data_ptr<float>(),
-                           want_logits ? (bf16raw*)logits.data_ptr() : nullptr, (int)B, (int)C,
-                           (int)H, (int)max_blocks, head_num_cus(), cur_stream()));
-  return {loss, dz_in, logits};
+  return head_loss<int64_t>("linear_head_ce", at::kLong, 1, launch_head_ce, y_in, w, bias, target,
+                            dw, db, want_logits, max_blocks);
 }
 
-// The regression twin (head_bwd.hip, head_mse_kernel): mean squared error
-// against a bf16 [B, C] target; returns (loss, dz_in, pred or an empty tensor).
+// The regression twin: mean squared error against a bf16 [B, C] target
+// (head_mse_kernel)
 std::tuple<at::Tensor, at::Tensor, at::Tensor> linear_head_mse(
     at::Tensor y_in, at::Tensor w, c10::optional<at::Tensor> bias, at::Tensor target,
     at::Tensor dw, c10::optional<at::Tensor> db, bool want_pred, int64_t max_blocks) {
-  check_gpu_contig(y_in, at::kBFloat16, "y_in");
-  check_gpu_contig(w, at::kBFloat16, "w");
-  check_gpu_contig(target, at::kBFloat16, "target");
-  check_gpu_contig(dw, at::kFloat, "dw");
-  TORCH_CHECK(y_in.dim() == 2 && w.dim() == 2 && target.dim() == 2);
-  int64_t B = y_in.size(0), H = y_in.size(1), C = w.size(0);
-  TORCH_CHECK(B >= 1 && B < (1LL << 31) && w.size(1) == H && target.size(0) == B &&
-                  target.size(1) == C && dw.dim() == 2 && dw.size(0) == C && dw.size(1) == H,
-              "shape mismatch");
-  TORCH_CHECK(head_bwd_ok(C, H), "linear_head_mse: unsupported (C, H); use the three-step route");
-  const float* bp = nullptr;
-  if (bias.has_value()) {
-    check_gpu_contig(*bias, at::kFloat, "bias");
-    TORCH_CHECK(bias->numel() == C);
-    bp = bias->data_ptr<float>();
-  }
-  float* dbp = nullptr;
-  if (db.has_value()) {
-    check_gpu_contig(*db, at::kFloat, "db");
-    TORCH_CHECK(db->numel() == C);
-    dbp = db->data_ptr<float>();
-  }
-  auto loss = at::empty({}, y_in.options().dtype(at::kFloat));
-  auto dz_in = at::empty({B, H}, y_in.options());
-  auto pred = want_pred ? at::empty({B, C}, y_in.options()) : at::empty({0}, y_in.options());
-  TORCH_CHECK(((uintptr_t)y_in.data_ptr() & 15) == 0 && ((uintptr_t)dz_in.data_ptr() & 15) == 0 &&
-                  ((uintptr_t)w.data_ptr() & 15) == 0,
-              "linear_head_mse wants 16-byte aligned activations and weights");
-  CHECK_HIP(launch_head_mse((const bf16raw*)w.data_ptr(), bp, (const bf16raw*)y_in.data_ptr(),
-                            (const bf16raw*)target.data_ptr(), (bf16raw*)dz_in.data_ptr(),
-                            dw.data_ptr<float>(), dbp, loss.data_ptr<float>(),
-                            want_pred ? (bf16raw*)pred.data_ptr() : nullptr, (int)B, (int)C,
-                            (int)H, (int)max_blocks, head_num_cus(), cur_stream()));
-  return {loss, dz_in, pred};
+  return head_loss<bf16raw>("linear_head_mse", at::kBFloat16, 2, launch_head_mse, y_in, w, bias,
+                            target, dw, db, want_pred, max_blocks);
 }
 
 // The last hidden layer's forward fused into the head's loss pass
@@ -740,38 +603,21 @@ std::tuple<at::Tensor, at::Tensor, at::Tensor, at::Tensor> linear_hidden_head_ce
               "shape mismatch");
   TORCH_CHECK(hidden_head_ce_ok(K, H, C),
               "linear_hidden_head_ce: unsupported (K_in, H, C); use linear_fwd + linear_head_ce");
-  const float *b2p = nullptr, *b3p = nullptr;
-  if (b2.has_value()) {
-    check_gpu_contig(*b2, at::kFloat, "b2");
-    TORCH_CHECK(b2->numel() == H);
-    b2p = b2->data_ptr<float>();
-  }
-  if (b3.has_value()) {
-    check_gpu_contig(*b3, at::kFloat, "b3");
-    TORCH_CHECK(b3->numel() == C);
-    b3p = b3->data_ptr<float>();
-  }
-  float* dbp = nullptr;
-  if (db3.has_value()) {
-    check_gpu_contig(*db3, at::kFloat, "db3");
-    TORCH_CHECK(db3->numel() == C);
-    dbp = db3->data_ptr<float>();
-  }
+  const float* b2p = opt_f32_vec(b2, H, "b2");
+  const float* b3p = opt_f32_vec(b3, C, "b3");
+  float* dbp = opt_f32_vec(db3, C, "db3");
   auto loss = at::empty({}, x.options().dtype(at::kFloat));
   auto dz = at::empty({B, H}, x.options());
   auto logits = want_logits ? at::empty({B, C}, x.options()) : at::empty({0}, x.options());
   auto h2 = want_h2 ? at::empty({B, H}, x.options()) : at::empty({0}, x.options());
-  TORCH_CHECK(((uintptr_t)x.data_ptr() & 15) == 0 && ((uintptr_t)w2.data_ptr() & 15) == 0 &&
-                  ((uintptr_t)w3.data_ptr() & 15) == 0 && ((uintptr_t)dz.data_ptr() & 15) == 0 &&
-                  (!want_h2 || ((uintptr_t)h2.data_ptr() & 15) == 0),
+  TORCH_CHECK(aligned16(x) && aligned16(w2) && aligned16(w3) && aligned16(dz) &&
+                  (!want_h2 || aligned16(h2)),
               "linear_hidden_head_ce wants 16-byte aligned activations and weights");
   CHECK_HIP(launch_hidden_head_ce(
-      (const bf16raw*)x.data_ptr(), (const bf16raw*)w2.data_ptr(), b2p,
-      (const bf16raw*)w3.data_ptr(), b3p, target.data_ptr<int64_t>(), (bf16raw*)dz.data_ptr(),
-      dw3.data_ptr<float>(), dbp, loss.data_ptr<float>(),
-      want_logits ? (bf16raw*)logits.data_ptr() : nullptr,
-      want_h2 ? (bf16raw*)h2.data_ptr() : nullptr, (int)B, (int)K, (int)H, (int)C,
-      (int)max_blocks, head_num_cus(), cur_stream()));
+      bf16_in(x), bf16_in(w2), b2p, bf16_in(w3), b3p, target.data_ptr<int64_t>(), bf16_out(dz),
+      dw3.data_ptr<float>(), dbp, loss.data_ptr<float>(), want_logits ? bf16_out(logits) : nullptr,
+      want_h2 ? bf16_out(h2) : nullptr, (int)B, (int)K, (int)H, (int)C, (int)max_blocks,
+      head_num_cus(), cur_stream()));
   return {loss, dz, logits, h2};
 }
 
@@ -794,23 +640,16 @@ std::tuple<at::Tensor, at::Tensor, at::Tensor> linear_mse(
                   target.size(1) == N,
               "shape mismatch");
   TORCH_CHECK(linear_mse_ok(N, H), "linear_mse: unsupported (N, H); use the two-step route");
-  const float* bp = nullptr;
-  if (bias.has_value()) {
-    check_gpu_contig(*bias, at::kFloat, "bias");
-    TORCH_CHECK(bias->numel() == N);
-    bp = bias->data_ptr<float>();
-  }
+  const float* bp = opt_f32_vec(bias, N, "bias");
   auto loss = at::empty({}, y_in.options().dtype(at::kFloat));
   auto dpred = at::empty({B, N}, y_in.options());
   auto pred = want_pred ? at::empty({B, N}, y_in.options()) : at::empty({0}, y_in.options());
   TORCH_CHECK(aligned16(y_in) && aligned16(w) && aligned16(target) && aligned16(dpred) &&
-                  (!want_pred || aligned16(pred)) && (((uintptr_t)bp) & 15) == 0,
+                  (!want_pred || aligned16(pred)) && (!bias.has_value() || aligned16(*bias)),
               "linear_mse wants 16-byte aligned operands");
-  CHECK_HIP(launch_linear_mse((const bf16raw*)y_in.data_ptr(), (const bf16raw*)w.data_ptr(), bp,
-                              (const bf16raw*)target.data_ptr(), (bf16raw*)dpred.data_ptr(),
-                              want_pred ? (bf16raw*)pred.data_ptr() : nullptr,
-                              loss.data_ptr<float>(), (int)B, (int)N, (int)H, (int)max_blocks,
-                              head_num_cus(), cur_stream()));
+  CHECK_HIP(launch_linear_mse(bf16_in(y_in), bf16_in(w), bp, bf16_in(target), bf16_out(dpred),
+                              want_pred ? bf16_out(pred) : nullptr, loss.data_ptr<float>(), (int)B,
+                              (int)N, (int)H, (int)max_blocks, head_num_cus(), cur_stream()));
   return {loss, dpred, pred};
 }
 
@@ -855,7 +694,7 @@ std::tuple<at::Tensor, c10::optional<at::Tensor>> mlp_predict(
     check_gpu_contig(w, at::kBFloat16, "weight");
     TORCH_CHECK(w.dim() == 2 && w.size(1) == k && w.device() == x.device(),
                 "shape mismatch along the chain at layer ", l);
-    wp[l] = (const bf16raw*)w.data_ptr();
+    wp[l] = bf16_in(w);
     aligned = aligned && aligned16(w);
     if (biases[l].has_value()) {
       check_gpu_contig(*biases[l], at::kFloat, "bias");
@@ -878,13 +717,13 @@ std::tuple<at::Tensor, c10::optional<at::Tensor>> mlp_predict(
   auto classes = at::empty({M}, x.options().dtype(at::kInt));
   c10::optional<at::Tensor> logits;
   if (want_logits) logits = at::empty({M, C}, x.options().dtype(at::kBFloat16));
-  bf16raw* lp = want_logits ? (bf16raw*)logits->data_ptr() : nullptr;
+  bf16raw* lp = want_logits ? bf16_out(*logits) : nullptr;
   if (x_f32) {
     CHECK_HIP(launch_mlp_predict_f32(x.data_ptr<float>(), wp, bp, wv, L, (int)K0, (int)C, M,
                                      classes.data_ptr<int>(), lp, (int)max_blocks,
                                      head_num_cus(), cur_stream()));
   } else {
-    CHECK_HIP(launch_mlp_predict((const bf16raw*)x.data_ptr(), wp, bp, wv, L, (int)K0, (int)C, M,
+    CHECK_HIP(launch_mlp_predict(bf16_in(x), wp, bp, wv, L, (int)K0, (int)C, M,
                                  classes.data_ptr<int>(), lp, (int)max_blocks, head_num_cus(),
                                  cur_stream()));
   }
@@ -913,7 +752,7 @@ at::Tensor linear_wgrad(at::Tensor dz, at::Tensor x, int64_t splitk) {
     auto dw = at::zeros({N, K}, x.options().dtype(at::kFloat));
     int S = small_wgrad_slices(B);
     auto scratch = at::empty({(int64_t)S * N * K}, x.options().dtype(at::kFloat));
-    CHECK_HIP(launch_small_wgrad((const bf16raw*)dz.data_ptr(), (const bf16raw*)x.data_ptr(),
+    CHECK_HIP(launch_small_wgrad(bf16_in(dz), bf16_in(x),
                                  dw.data_ptr<float>(), scratch.data_ptr<float>(), S, B, (int)N,
                                  (int)K, cur_stream()));
     return dw;
@@ -939,7 +778,7 @@ void linear_wgrad_into(at::Tensor dz, at::Tensor x, at::Tensor dw, int64_t split
   if (small_wgrad_path(B, N, K)) {
     int S = small_wgrad_slices(B);
     auto scratch = at::empty({(int64_t)S * N * K}, x.options().dtype(at::kFloat));
-    CHECK_HIP(launch_small_wgrad((const bf16raw*)dz.data_ptr(), (const bf16raw*)x.data_ptr(),
+    CHECK_HIP(launch_small_wgrad(bf16_in(dz), bf16_in(x),
                                  dw.data_ptr<float>(), scratch.data_ptr<float>(), S, B, (int)N,
                                  (int)K, cur_stream()));
     return;
@@ -966,105 +805,73 @@ void linear_wgrad_bias_into(at::Tensor dz, at::Tensor x, at::Tensor dw, at::Tens
                              db.data_ptr<float>(), (int)K, cur_stream()));
 }
 
-// Batch-streaming dW (+ db) for big-batch Linear layers (linear_wgrad.hip);
-// same contract as linear_wgrad_into / linear_wgrad_bias_into: the caller
-// zeroes, a second call adds.  linear_wgrad_stream_ok is the routing rule
-// (shape set and measured batch threshold); the launcher itself serves every
-// batch that linear_wgrad_stream_runs accepts.
-bool linear_wgrad_stream_runs(int64_t No, int64_t Ki, int64_t B) {
-  return No <= 256 && Ki < (1 << 24) && linear_wgrad_stream_can_run((int)No, (int)Ki, B) != 0;
+// Batch-streaming dW (+ db) for big-batch Linear layers; same contract as
+// linear_wgrad_into / linear_wgrad_bias_into: the caller zeroes, a second call
+// adds.  Three kernels: linear_wgrad.hip (No <= 256), linear_wgrad_wide.hip (a
+// wide layer on a 64/128/256-wide input, which the first cannot hold) and
+// hidden_bwd.hip (the first with the masked dgrad of a hidden layer added).
+// For each, *_ok is the routing rule (shape set and measured batch
+// threshold); the launcher itself serves every batch that *_runs accepts.
+constexpr auto linear_wgrad_stream_runs = shape_pred<narrow_fits, linear_wgrad_stream_can_run>;
+constexpr auto linear_wgrad_stream_ok = shape_pred<narrow_fits, linear_wgrad_stream_supported>;
+constexpr auto linear_wgrad_wide_runs = shape_pred<wide_fits, linear_wgrad_wide_can_run>;
+constexpr auto linear_wgrad_wide_ok = shape_pred<wide_fits, linear_wgrad_wide_supported>;
+constexpr auto linear_hidden_bwd_runs = shape_pred<narrow_fits, hidden_bwd_can_run>;
+constexpr auto linear_hidden_bwd_ok = shape_pred<narrow_fits, hidden_bwd_supported>;
+
+// What the three ask of their common operands: dz [B, No] and x [B, Ki] bf16,
+// dw [No, Ki] and the optional db [No] fp32.
+struct StreamWgradArgs {
+  int64_t B, N, K;
+  float* dbp;
+};
+
+static StreamWgradArgs check_stream_wgrad(const at::Tensor& dz, const at::Tensor& x,
+                                          const char* x_name, const at::Tensor& dw,
+                                          const c10::optional<at::Tensor>& db) {
+  check_gpu_contig(dz, at::kBFloat16, "dz");
+  check_gpu_contig(x, at::kBFloat16, x_name);
+  check_gpu_contig(dw, at::kFloat, "dw");
+  TORCH_CHECK(dz.dim() == 2 && x.dim() == 2);
+  int64_t B = dz.size(0), N = dz.size(1), K = x.size(1);
+  TORCH_CHECK(x.size(0) == B && dw.size(0) == N && dw.size(1) == K, "shape mismatch");
+  return {B, N, K, opt_f32_vec(db, N, "db")};
 }
-bool linear_wgrad_stream_ok(int64_t No, int64_t Ki, int64_t B) {
-  return No <= 256 && Ki < (1 << 24) && linear_wgrad_stream_supported((int)No, (int)Ki, B) != 0;
+
+static void stream_wgrad(const char* name, bool (*runs)(int64_t, int64_t, int64_t),
+                         hipError_t (*launch)(const bf16raw*, const bf16raw*, float*, float*,
+                                              int64_t, int, int, int, int, hipStream_t),
+                         const at::Tensor& dz, const at::Tensor& x, const at::Tensor& dw,
+                         const c10::optional<at::Tensor>& db, int64_t max_blocks) {
+  const StreamWgradArgs a = check_stream_wgrad(dz, x, "x", dw, db);
+  TORCH_CHECK(runs(a.N, a.K, a.B), name, ": unsupported (No, Ki, B); use linear_wgrad_into");
+  TORCH_CHECK(aligned16(dz) && aligned16(x), name, " wants 16-byte aligned dz and x");
+  CHECK_HIP(launch(bf16_in(dz), bf16_in(x), dw.data_ptr<float>(), a.dbp, a.B, (int)a.N, (int)a.K,
+                   (int)max_blocks, head_num_cus(), cur_stream()));
 }
 
 void linear_wgrad_stream(at::Tensor dz, at::Tensor x, at::Tensor dw, c10::optional<at::Tensor> db,
                          int64_t max_blocks) {
-  check_gpu_contig(dz, at::kBFloat16, "dz");
-  check_gpu_contig(x, at::kBFloat16, "x");
-  check_gpu_contig(dw, at::kFloat, "dw");
-  TORCH_CHECK(dz.dim() == 2 && x.dim() == 2);
-  int64_t B = dz.size(0), N = dz.size(1), K = x.size(1);
-  TORCH_CHECK(x.size(0) == B && dw.size(0) == N && dw.size(1) == K, "shape mismatch");
-  float* dbp = nullptr;
-  if (db.has_value()) {
-    check_gpu_contig(*db, at::kFloat, "db");
-    TORCH_CHECK(db->numel() == N);
-    dbp = db->data_ptr<float>();
-  }
-  TORCH_CHECK(linear_wgrad_stream_runs(N, K, B),
-              "linear_wgrad_stream: unsupported (No, Ki, B); use linear_wgrad_into");
-  TORCH_CHECK(((uintptr_t)dz.data_ptr() & 15) == 0 && ((uintptr_t)x.data_ptr() & 15) == 0,
-              "linear_wgrad_stream wants 16-byte aligned dz and x");
-  CHECK_HIP(launch_linear_wgrad_stream((const bf16raw*)dz.data_ptr(), (const bf16raw*)x.data_ptr(),
-                                       dw.data_ptr<float>(), dbp, B, (int)N, (int)K,
-                                       (int)max_blocks, head_num_cus(), cur_stream()));
-}
-
-// The same contract for a wide layer on a 64/128/256-wide input
-// (linear_wgrad_wide.hip), which linear_wgrad_stream cannot hold:
-// linear_wgrad_wide_ok is the routing rule (No > 256 and the measured batch
-// threshold); the launcher serves every shape linear_wgrad_wide_runs accepts.
-bool linear_wgrad_wide_runs(int64_t No, int64_t Ki, int64_t B) {
-  return No < (1 << 24) && Ki <= 256 && linear_wgrad_wide_can_run((int)No, (int)Ki, B) != 0;
-}
-bool linear_wgrad_wide_ok(int64_t No, int64_t Ki, int64_t B) {
-  return No < (1 << 24) && Ki <= 256 && linear_wgrad_wide_supported((int)No, (int)Ki, B) != 0;
+  stream_wgrad("linear_wgrad_stream", linear_wgrad_stream_runs, launch_linear_wgrad_stream, dz, x,
+               dw, db, max_blocks);
 }
 
 void linear_wgrad_wide(at::Tensor dz, at::Tensor x, at::Tensor dw, c10::optional<at::Tensor> db,
                        int64_t max_blocks) {
-  check_gpu_contig(dz, at::kBFloat16, "dz");
-  check_gpu_contig(x, at::kBFloat16, "x");
-  check_gpu_contig(dw, at::kFloat, "dw");
-  TORCH_CHECK(dz.dim() == 2 && x.dim() == 2);
-  int64_t B = dz.size(0), N = dz.size(1), K = x.size(1);
-  TORCH_CHECK(x.size(0) == B && dw.size(0) == N && dw.size(1) == K, "shape mismatch");
-  float* dbp = nullptr;
-  if (db.has_value()) {
-    check_gpu_contig(*db, at::kFloat, "db");
-    TORCH_CHECK(db->numel() == N);
-    dbp = db->data_ptr<float>();
-  }
-  TORCH_CHECK(linear_wgrad_wide_runs(N, K, B),
-              "linear_wgrad_wide: unsupported (No, Ki, B); use linear_wgrad_into");
-  TORCH_CHECK(((uintptr_t)dz.data_ptr() & 15) == 0 && ((uintptr_t)x.data_ptr() & 15) == 0,
-              "linear_wgrad_wide wants 16-byte aligned dz and x");
-  CHECK_HIP(launch_linear_wgrad_wide((const bf16raw*)dz.data_ptr(), (const bf16raw*)x.data_ptr(),
-                                     dw.data_ptr<float>(), dbp, B, (int)N, (int)K,
-                                     (int)max_blocks, head_num_cus(), cur_stream()));
+  stream_wgrad("linear_wgrad_wide", linear_wgrad_wide_runs, launch_linear_wgrad_wide, dz, x, dw,
+               db, max_blocks);
 }
 
 // One-pass backward of a hidden Linear on a ReLU output (hidden_bwd.hip):
 // returns dz_in = (dz @ w) * (x_in > 0), bit-identical to linear_dgrad_relu,
 // and accumulates dw / db under linear_wgrad_stream's contract.
-// linear_hidden_bwd_ok is the routing rule (shape set and measured batch
-// threshold); the launcher serves every batch linear_hidden_bwd_runs accepts.
-bool linear_hidden_bwd_runs(int64_t No, int64_t Ki, int64_t B) {
-  return No <= 256 && Ki < (1 << 24) && hidden_bwd_can_run((int)No, (int)Ki, B) != 0;
-}
-bool linear_hidden_bwd_ok(int64_t No, int64_t Ki, int64_t B) {
-  return No <= 256 && Ki < (1 << 24) && hidden_bwd_supported((int)No, (int)Ki, B) != 0;
-}
-
 at::Tensor linear_hidden_bwd(at::Tensor dz, at::Tensor w, at::Tensor x_in, at::Tensor dw,
                              c10::optional<at::Tensor> db, int64_t max_blocks,
                              c10::optional<at::Tensor> out) {
-  check_gpu_contig(dz, at::kBFloat16, "dz");
   check_gpu_contig(w, at::kBFloat16, "w");
-  check_gpu_contig(x_in, at::kBFloat16, "x_in");
-  check_gpu_contig(dw, at::kFloat, "dw");
-  TORCH_CHECK(dz.dim() == 2 && x_in.dim() == 2 && w.dim() == 2);
-  int64_t B = dz.size(0), N = dz.size(1), K = x_in.size(1);
-  TORCH_CHECK(x_in.size(0) == B && w.size(0) == N && w.size(1) == K && dw.size(0) == N &&
-                  dw.size(1) == K,
-              "shape mismatch");
-  float* dbp = nullptr;
-  if (db.has_value()) {
-    check_gpu_contig(*db, at::kFloat, "db");
-    TORCH_CHECK(db->numel() == N);
-    dbp = db->data_ptr<float>();
-  }
+  const StreamWgradArgs a = check_stream_wgrad(dz, x_in, "x_in", dw, db);
+  const int64_t B = a.B, N = a.N, K = a.K;
+  TORCH_CHECK(w.dim() == 2 && w.size(0) == N && w.size(1) == K, "shape mismatch");
   TORCH_CHECK(linear_hidden_bwd_runs(N, K, B),
               "linear_hidden_bwd: unsupported (No, Ki, B); use linear_dgrad_relu and "
               "linear_wgrad_into");
@@ -1080,9 +887,8 @@ at::Tensor linear_hidden_bwd(at::Tensor dz, at::Tensor w, at::Tensor x_in, at::T
   } else {
     dz_in = at::empty({B, K}, dz.options());
   }
-  CHECK_HIP(launch_hidden_bwd((const bf16raw*)dz.data_ptr(), (const bf16raw*)x_in.data_ptr(),
-                              (const bf16raw*)w.data_ptr(), (bf16raw*)dz_in.data_ptr(),
-                              dw.data_ptr<float>(), dbp, B, (int)N, (int)K, (int)max_blocks,
+  CHECK_HIP(launch_hidden_bwd(bf16_in(dz), bf16_in(x_in), bf16_in(w), bf16_out(dz_in),
+                              dw.data_ptr<float>(), a.dbp, B, (int)N, (int)K, (int)max_blocks,
                               head_num_cus(), cur_stream()));
   return dz_in;
 }
@@ -1101,26 +907,13 @@ void bias_grad_into(at::Tensor dz, at::Tensor db) {
     scratch = at::empty({(int64_t)S * N}, dz.options().dtype(at::kFloat));
     sp = scratch.data_ptr<float>();
   }
-  CHECK_HIP(launch_bias_grad((const bf16raw*)dz.data_ptr(), db.data_ptr<float>(), (int)M, N, sp,
+  CHECK_HIP(launch_bias_grad(bf16_in(dz), db.data_ptr<float>(), (int)M, N, sp,
                              S, cur_stream()));
 }
 
 // ---------------------------------------------------------------------------
 // Conv2d lowering + pooling + dropout (conv.hip)
 // ---------------------------------------------------------------------------
-
-extern "C" {
-hipError_t launch_im2col(const bf16raw*, bf16raw*, int, int, int, int, int, int, int, int, int,
-                         int, int, int, hipStream_t);
-hipError_t launch_col2im(const bf16raw*, bf16raw*, int, int, int, int, int, int, int, int, int,
-                         int, int, int, hipStream_t);
-hipError_t launch_maxpool_fwd(const bf16raw*, bf16raw*, uint8_t*, int, int, int, int, int, int,
-                              hipStream_t);
-hipError_t launch_maxpool_bwd(const bf16raw*, const uint8_t*, bf16raw*, int, int, int, int, int,
-                              int, hipStream_t);
-hipError_t launch_dropout(const bf16raw*, bf16raw*, int64_t, int64_t, int64_t, float,
-                          uint32_t, hipStream_t);
-}
 
 at::Tensor im2col(at::Tensor x, int64_t KH, int64_t KW, int64_t sh, int64_t sw, int64_t ph,
                   int64_t pw) {
@@ -1130,7 +923,7 @@ at::Tensor im2col(at::Tensor x, int64_t KH, int64_t KW, int64_t sh, int64_t sw, 
   int64_t HO = (H + 2 * ph - KH) / sh + 1;
   int64_t WO = (W + 2 * pw - KW) / sw + 1;
   auto col = at::empty({B * HO * WO, CI * KH * KW}, x.options());
-  CHECK_HIP(launch_im2col((const bf16raw*)x.data_ptr(), (bf16raw*)col.data_ptr(), (int)B, (int)CI,
+  CHECK_HIP(launch_im2col(bf16_in(x), bf16_out(col), (int)B, (int)CI,
                           (int)H, (int)W, (int)KH, (int)KW, (int)HO, (int)WO, (int)sh, (int)sw,
                           (int)ph, (int)pw, cur_stream()));
   return col;
@@ -1143,7 +936,7 @@ at::Tensor col2im(at::Tensor dcol, int64_t B, int64_t CI, int64_t H, int64_t W, 
   int64_t WO = (W + 2 * pw - KW) / sw + 1;
   TORCH_CHECK(dcol.size(0) == B * HO * WO && dcol.size(1) == CI * KH * KW);
   auto dx = at::empty({B, CI, H, W}, dcol.options());
-  CHECK_HIP(launch_col2im((const bf16raw*)dcol.data_ptr(), (bf16raw*)dx.data_ptr(), (int)B,
+  CHECK_HIP(launch_col2im(bf16_in(dcol), bf16_out(dx), (int)B,
                           (int)CI, (int)H, (int)W, (int)KH, (int)KW, (int)HO, (int)WO, (int)sh,
                           (int)sw, (int)ph, (int)pw, cur_stream()));
   return dx;
@@ -1156,7 +949,7 @@ std::tuple<at::Tensor, at::Tensor> maxpool_fwd(at::Tensor x, int64_t ks) {
   int64_t HO = H / ks, WO = W / ks;
   auto y = at::empty({B, C, HO, WO}, x.options());
   auto arg = at::empty({B, C, HO, WO}, x.options().dtype(at::kByte));
-  CHECK_HIP(launch_maxpool_fwd((const bf16raw*)x.data_ptr(), (bf16raw*)y.data_ptr(),
+  CHECK_HIP(launch_maxpool_fwd(bf16_in(x), bf16_out(y),
                                arg.data_ptr<uint8_t>(), (int)(B * C), (int)H, (int)W, (int)ks,
                                (int)HO, (int)WO, cur_stream()));
   return {y, arg};
@@ -1167,8 +960,8 @@ at::Tensor maxpool_bwd(at::Tensor dy, at::Tensor arg, int64_t H, int64_t W, int6
   int64_t B = dy.size(0), C = dy.size(1);
   auto dx = at::empty({B, C, H, W}, dy.options());
   // windows are disjoint (stride == kernel): bwd writes every slot, no zero
-  CHECK_HIP(launch_maxpool_bwd((const bf16raw*)dy.data_ptr(), arg.data_ptr<uint8_t>(),
-                               (bf16raw*)dx.data_ptr(), (int)(B * C), (int)H, (int)W, (int)ks,
+  CHECK_HIP(launch_maxpool_bwd(bf16_in(dy), arg.data_ptr<uint8_t>(),
+                               bf16_out(dx), (int)(B * C), (int)H, (int)W, (int)ks,
                                (int)dy.size(2), (int)dy.size(3), cur_stream()));
   // rows/cols beyond HO*ks / WO*ks (non-divisible inputs) keep garbage: zero
   if (H % ks || W % ks) {
@@ -1182,7 +975,7 @@ at::Tensor dropout_apply(at::Tensor x, double p, int64_t seed, int64_t units_div
                          int64_t cmod) {
   check_gpu_contig(x, at::kBFloat16, "x");
   auto y = at::empty_like(x);
-  CHECK_HIP(launch_dropout((const bf16raw*)x.data_ptr(), (bf16raw*)y.data_ptr(), x.numel(),
+  CHECK_HIP(launch_dropout(bf16_in(x), bf16_out(y), x.numel(),
                            units_div, cmod, (float)p, (uint32_t)(seed & 0xffffffff),
                            cur_stream()));
   return y;
@@ -1236,7 +1029,7 @@ std::tuple<at::Tensor, at::Tensor> bn_stats(at::Tensor x, c10::optional<at::Tens
     rm = running_mean->data_ptr<float>();
     rv = running_var->data_ptr<float>();
   }
-  CHECK_HIP(launch_bn_stats((const bf16raw*)x.data_ptr(), sum.data_ptr<float>(),
+  CHECK_HIP(launch_bn_stats(bf16_in(x), sum.data_ptr<float>(),
                             sumsq.data_ptr<float>(), mean.data_ptr<float>(),
                             invstd.data_ptr<float>(), rm, rv, B, C, HW, (float)momentum,
                             (float)eps, bn_split(C), cur_stream()));
@@ -1251,10 +1044,10 @@ at::Tensor bn_apply(at::Tensor x, c10::optional<at::Tensor> res, at::Tensor mean
   if (res.has_value()) {
     check_gpu_contig(*res, at::kBFloat16, "res");
     TORCH_CHECK(res->sizes() == x.sizes(), "residual shape mismatch");
-    rp = (const bf16raw*)res->data_ptr();
+    rp = bf16_in(*res);
   }
   auto y = at::empty_like(x);
-  CHECK_HIP(launch_bn_apply((const bf16raw*)x.data_ptr(), rp, (bf16raw*)y.data_ptr(),
+  CHECK_HIP(launch_bn_apply(bf16_in(x), rp, bf16_out(y),
                             mean.data_ptr<float>(), invstd.data_ptr<float>(),
                             gamma.data_ptr<float>(), beta.data_ptr<float>(), (int)x.size(1),
                             x.size(2) * x.size(3), x.numel(), relu ? 1 : 0, cur_stream()));
@@ -1271,10 +1064,10 @@ void bn_bwd_reduce(at::Tensor dy, c10::optional<at::Tensor> yrelu, at::Tensor x,
   check_gpu_contig(dbeta, at::kFloat, "dbeta");
   check_gpu_contig(dgamma, at::kFloat, "dgamma");
   const bf16raw* yp = nullptr;
-  if (yrelu.has_value()) yp = (const bf16raw*)yrelu->data_ptr();
+  if (yrelu.has_value()) yp = bf16_in(*yrelu);
   int B = (int)x.size(0), C = (int)x.size(1);
   int64_t HW = x.size(2) * x.size(3);
-  CHECK_HIP(launch_bn_bwd_reduce((const bf16raw*)dy.data_ptr(), yp, (const bf16raw*)x.data_ptr(),
+  CHECK_HIP(launch_bn_bwd_reduce(bf16_in(dy), yp, bf16_in(x),
                                  mean.data_ptr<float>(), invstd.data_ptr<float>(),
                                  dbeta.data_ptr<float>(), dgamma.data_ptr<float>(), B, C, HW,
                                  bn_split(C), cur_stream()));
@@ -1286,15 +1079,15 @@ at::Tensor bn_bwd_dx(at::Tensor dy, c10::optional<at::Tensor> yrelu, at::Tensor 
   check_gpu_contig(dy, at::kBFloat16, "dy");
   check_gpu_contig(x, at::kBFloat16, "x");
   const bf16raw* yp = nullptr;
-  if (yrelu.has_value()) yp = (const bf16raw*)yrelu->data_ptr();
+  if (yrelu.has_value()) yp = bf16_in(*yrelu);
   int C = (int)x.size(1);
   int64_t HW = x.size(2) * x.size(3);
   auto dx = at::empty_like(x);
   float inv_count = 1.0f / (float)(x.size(0) * HW);
-  CHECK_HIP(launch_bn_bwd_dx((const bf16raw*)dy.data_ptr(), yp, (const bf16raw*)x.data_ptr(),
+  CHECK_HIP(launch_bn_bwd_dx(bf16_in(dy), yp, bf16_in(x),
                              mean.data_ptr<float>(), invstd.data_ptr<float>(),
                              gamma.data_ptr<float>(), dbeta.data_ptr<float>(),
-                             dgamma.data_ptr<float>(), (bf16raw*)dx.data_ptr(), C, HW, x.numel(),
+                             dgamma.data_ptr<float>(), bf16_out(dx), C, HW, x.numel(),
                              inv_count, train_stats ? 1 : 0, cur_stream()));
   return dx;
 }
@@ -1304,8 +1097,8 @@ at::Tensor add_relu(at::Tensor a, at::Tensor b) {
   check_gpu_contig(b, at::kBFloat16, "b");
   TORCH_CHECK(a.sizes() == b.sizes());
   auto out = at::empty_like(a);
-  CHECK_HIP(launch_add_relu((const bf16raw*)a.data_ptr(), (const bf16raw*)b.data_ptr(),
-                            (bf16raw*)out.data_ptr(), a.numel(), cur_stream()));
+  CHECK_HIP(launch_add_relu(bf16_in(a), bf16_in(b),
+                            bf16_out(out), a.numel(), cur_stream()));
   return out;
 }
 
@@ -1320,7 +1113,7 @@ std::tuple<at::Tensor, at::Tensor> maxpool_gen_fwd(at::Tensor x, int64_t ks, int
   int64_t BC = x.size(0) * x.size(1);
   auto y = at::empty({x.size(0), x.size(1), HO, WO}, x.options());
   auto arg = at::empty({x.size(0), x.size(1), HO, WO}, x.options().dtype(at::kByte));
-  CHECK_HIP(launch_maxpool_gen_fwd((const bf16raw*)x.data_ptr(), (bf16raw*)y.data_ptr(),
+  CHECK_HIP(launch_maxpool_gen_fwd(bf16_in(x), bf16_out(y),
                                    arg.data_ptr<uint8_t>(), BC, H, W, HO, WO, (int)ks,
                                    (int)stride, (int)pad, cur_stream()));
   return {y, arg};
@@ -1333,8 +1126,8 @@ at::Tensor maxpool_gen_bwd(at::Tensor dy, at::Tensor arg, int64_t H, int64_t W, 
   int HO = (int)dy.size(2), WO = (int)dy.size(3);
   int64_t BC = dy.size(0) * dy.size(1);
   auto dx = at::empty({dy.size(0), dy.size(1), H, W}, dy.options());
-  CHECK_HIP(launch_maxpool_gen_bwd((const bf16raw*)dy.data_ptr(), arg.data_ptr<uint8_t>(),
-                                   (bf16raw*)dx.data_ptr(), BC, (int)H, (int)W, HO, WO, (int)ks,
+  CHECK_HIP(launch_maxpool_gen_bwd(bf16_in(dy), arg.data_ptr<uint8_t>(),
+                                   bf16_out(dx), BC, (int)H, (int)W, HO, WO, (int)ks,
                                    (int)stride, (int)pad, cur_stream()));
   return dx;
 }
@@ -1343,7 +1136,7 @@ at::Tensor gap_fwd(at::Tensor x) {
   check_gpu_contig(x, at::kBFloat16, "x");
   TORCH_CHECK(x.dim() == 4, "x must be NCHW");
   auto y = at::empty({x.size(0), x.size(1)}, x.options());
-  CHECK_HIP(launch_gap_fwd((const bf16raw*)x.data_ptr(), (bf16raw*)y.data_ptr(),
+  CHECK_HIP(launch_gap_fwd(bf16_in(x), bf16_out(y),
                            x.size(0) * x.size(1), x.size(2) * x.size(3), cur_stream()));
   return y;
 }
@@ -1351,7 +1144,7 @@ at::Tensor gap_fwd(at::Tensor x) {
 at::Tensor gap_bwd(at::Tensor dy, int64_t H, int64_t W) {
   check_gpu_contig(dy, at::kBFloat16, "dy");
   auto dx = at::empty({dy.size(0), dy.size(1), H, W}, dy.options());
-  CHECK_HIP(launch_gap_bwd((const bf16raw*)dy.data_ptr(), (bf16raw*)dx.data_ptr(), H * W,
+  CHECK_HIP(launch_gap_bwd(bf16_in(dy), bf16_out(dx), H * W,
                            dx.numel(), cur_stream()));
   return dx;
 }
@@ -1373,7 +1166,7 @@ at::Tensor im2col_nhwc(at::Tensor x, int64_t KH, int64_t KW, int64_t sh, int64_t
   int64_t Kp = (K + 7) & ~7LL;
   // pad columns are zeroed by the im2col kernels themselves
   auto col = at::empty({(int64_t)B * HO * WO, Kp}, x.options());
-  CHECK_HIP(launch_im2col_nhwc((const bf16raw*)x.data_ptr(), (bf16raw*)col.data_ptr(), B, CI, H,
+  CHECK_HIP(launch_im2col_nhwc(bf16_in(x), bf16_out(col), B, CI, H,
                                W, (int)KH, (int)KW, HO, WO, (int)sh, (int)sw, (int)ph, (int)pw,
                                (int)Kp, cur_stream()));
   return col;
@@ -1387,7 +1180,7 @@ at::Tensor col2im_nhwc(at::Tensor dcol, int64_t B, int64_t CI, int64_t H, int64_
   int Kp = (int)dcol.size(1);  // row stride (K padded to x8)
   TORCH_CHECK(Kp >= KH * KW * CI, "dcol narrower than K");
   auto dx = at::empty({B, H, W, CI}, dcol.options());
-  CHECK_HIP(launch_col2im_nhwc((const bf16raw*)dcol.data_ptr(), (bf16raw*)dx.data_ptr(), (int)B,
+  CHECK_HIP(launch_col2im_nhwc(bf16_in(dcol), bf16_out(dx), (int)B,
                                (int)CI, (int)H, (int)W, (int)KH, (int)KW, HO, WO, (int)sh,
                                (int)sw, (int)ph, (int)pw, Kp, cur_stream()));
   return dx;
@@ -1403,7 +1196,7 @@ std::tuple<at::Tensor, at::Tensor> maxpool_nhwc_fwd(at::Tensor x, int64_t ks, in
   int WO = (int)((W + 2 * pad - ks) / stride + 1);
   auto y = at::empty({B, HO, WO, C}, x.options());
   auto arg = at::empty({B, HO, WO, C}, x.options().dtype(at::kByte));
-  CHECK_HIP(launch_maxpool_nhwc_fwd((const bf16raw*)x.data_ptr(), (bf16raw*)y.data_ptr(),
+  CHECK_HIP(launch_maxpool_nhwc_fwd(bf16_in(x), bf16_out(y),
                                     arg.data_ptr<uint8_t>(), B, C, H, W, HO, WO, (int)ks,
                                     (int)stride, (int)pad, cur_stream()));
   return {y, arg};
@@ -1415,8 +1208,8 @@ at::Tensor maxpool_nhwc_bwd(at::Tensor dy, at::Tensor arg, int64_t H, int64_t W,
   check_gpu_contig(arg, at::kByte, "arg");
   int B = (int)dy.size(0), HO = (int)dy.size(1), WO = (int)dy.size(2), C = (int)dy.size(3);
   auto dx = at::empty({B, H, W, (int64_t)C}, dy.options());
-  CHECK_HIP(launch_maxpool_nhwc_bwd((const bf16raw*)dy.data_ptr(), arg.data_ptr<uint8_t>(),
-                                    (bf16raw*)dx.data_ptr(), B, C, (int)H, (int)W, HO, WO,
+  CHECK_HIP(launch_maxpool_nhwc_bwd(bf16_in(dy), arg.data_ptr<uint8_t>(),
+                                    bf16_out(dx), B, C, (int)H, (int)W, HO, WO,
                                     (int)ks, (int)stride, (int)pad, cur_stream()));
   return dx;
 }
@@ -1426,7 +1219,7 @@ at::Tensor gap_nhwc_fwd(at::Tensor x) {
   TORCH_CHECK(x.dim() == 4, "x must be BHWC");
   int B = (int)x.size(0), C = (int)x.size(3);
   auto y = at::empty({B, C}, x.options());
-  CHECK_HIP(launch_gap_nhwc_fwd((const bf16raw*)x.data_ptr(), (bf16raw*)y.data_ptr(), B, C,
+  CHECK_HIP(launch_gap_nhwc_fwd(bf16_in(x), bf16_out(y), B, C,
                                 x.size(1) * x.size(2), cur_stream()));
   return y;
 }
@@ -1435,7 +1228,7 @@ at::Tensor gap_nhwc_bwd(at::Tensor dy, int64_t H, int64_t W) {
   check_gpu_contig(dy, at::kBFloat16, "dy");
   int B = (int)dy.size(0), C = (int)dy.size(1);
   auto dx = at::empty({B, H, W, (int64_t)C}, dy.options());
-  CHECK_HIP(launch_gap_nhwc_bwd((const bf16raw*)dy.data_ptr(), (bf16raw*)dx.data_ptr(), B, C,
+  CHECK_HIP(launch_gap_nhwc_bwd(bf16_in(dy), bf16_out(dx), B, C,
                                 H * W, cur_stream()));
   return dx;
 }
@@ -1479,7 +1272,7 @@ std::tuple<at::Tensor, at::Tensor> bn_stats_nhwc(at::Tensor x,
     scratch = at::empty({2LL * S * C}, fopt);
     sp = scratch.data_ptr<float>();
   }
-  CHECK_HIP(launch_bn_stats_nhwc((const bf16raw*)x.data_ptr(), sum.data_ptr<float>(),
+  CHECK_HIP(launch_bn_stats_nhwc(bf16_in(x), sum.data_ptr<float>(),
                                  sumsq.data_ptr<float>(), mean.data_ptr<float>(),
                                  invstd.data_ptr<float>(), rm, rv, M, C, (float)momentum,
                                  (float)eps, nsplit, sp, S, cur_stream()));
@@ -1494,10 +1287,10 @@ at::Tensor bn_apply_nhwc(at::Tensor x, c10::optional<at::Tensor> res, at::Tensor
   if (res.has_value()) {
     check_gpu_contig(*res, at::kBFloat16, "res");
     TORCH_CHECK(res->sizes() == x.sizes(), "residual shape mismatch");
-    rp = (const bf16raw*)res->data_ptr();
+    rp = bf16_in(*res);
   }
   auto y = at::empty_like(x);
-  CHECK_HIP(launch_bn_apply_nhwc((const bf16raw*)x.data_ptr(), rp, (bf16raw*)y.data_ptr(),
+  CHECK_HIP(launch_bn_apply_nhwc(bf16_in(x), rp, bf16_out(y),
                                  mean.data_ptr<float>(), invstd.data_ptr<float>(),
                                  gamma.data_ptr<float>(), beta.data_ptr<float>(),
                                  (int)x.size(3), x.numel(), relu ? 1 : 0, cur_stream()));
@@ -1512,7 +1305,7 @@ void bn_bwd_reduce_nhwc(at::Tensor dy, c10::optional<at::Tensor> yrelu, at::Tens
   check_gpu_contig(dbeta, at::kFloat, "dbeta");
   check_gpu_contig(dgamma, at::kFloat, "dgamma");
   const bf16raw* yp = nullptr;
-  if (yrelu.has_value()) yp = (const bf16raw*)yrelu->data_ptr();
+  if (yrelu.has_value()) yp = bf16_in(*yrelu);
   int C = (int)x.size(3);
   int64_t M = x.numel() / C;
   int tiles = (C + 63) / 64;
@@ -1526,8 +1319,8 @@ void bn_bwd_reduce_nhwc(at::Tensor dy, c10::optional<at::Tensor> yrelu, at::Tens
     scratch = at::empty({2LL * S * C}, x.options().dtype(at::kFloat));
     sp = scratch.data_ptr<float>();
   }
-  CHECK_HIP(launch_bn_bwd_reduce_nhwc((const bf16raw*)dy.data_ptr(), yp,
-                                      (const bf16raw*)x.data_ptr(), mean.data_ptr<float>(),
+  CHECK_HIP(launch_bn_bwd_reduce_nhwc(bf16_in(dy), yp,
+                                      bf16_in(x), mean.data_ptr<float>(),
                                       invstd.data_ptr<float>(), gamma.data_ptr<float>(),
                                       beta.data_ptr<float>(), dbeta.data_ptr<float>(),
                                       dgamma.data_ptr<float>(), M, C, nsplit, sp, S,
@@ -1540,15 +1333,15 @@ at::Tensor bn_bwd_dx_nhwc(at::Tensor dy, c10::optional<at::Tensor> yrelu, at::Te
   check_gpu_contig(dy, at::kBFloat16, "dy");
   check_gpu_contig(x, at::kBFloat16, "x");
   const bf16raw* yp = nullptr;
-  if (yrelu.has_value()) yp = (const bf16raw*)yrelu->data_ptr();
+  if (yrelu.has_value()) yp = bf16_in(*yrelu);
   int C = (int)x.size(3);
   auto dx = at::empty_like(x);
   float inv_count = 1.0f / (float)(x.numel() / C);
-  CHECK_HIP(launch_bn_bwd_dx_nhwc((const bf16raw*)dy.data_ptr(), yp,
-                                  (const bf16raw*)x.data_ptr(), mean.data_ptr<float>(),
+  CHECK_HIP(launch_bn_bwd_dx_nhwc(bf16_in(dy), yp,
+                                  bf16_in(x), mean.data_ptr<float>(),
                                   invstd.data_ptr<float>(), gamma.data_ptr<float>(),
                                   beta.data_ptr<float>(), dbeta.data_ptr<float>(),
-                                  dgamma.data_ptr<float>(), (bf16raw*)dx.data_ptr(), C,
+                                  dgamma.data_ptr<float>(), bf16_out(dx), C,
                                   x.numel(), inv_count, train_stats ? 1 : 0, cur_stream()));
   return dx;
 }
@@ -1583,27 +1376,23 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("bias"), py::arg("relu"), py::arg("allow_stream") = true);
   m.def("linear_dgrad", &linear_dgrad, "dX = dZ W, MFMA", py::arg("dz"), py::arg("w"),
         py::arg("allow_stream") = true);
-  m.def("linear_fwd_stream_supported", &linear_fwd_stream_ok,
+  m.def("linear_fwd_stream_supported", linear_fwd_stream_ok,
         "can the full-N streaming Linear kernel compute C[M, N] from a K-deep reduction",
         py::arg("N"), py::arg("K"), py::arg("M"));
-  m.def("linear_fwd_stream_min_rows", &linear_stream_min_rows,
+  m.def("linear_fwd_stream_min_rows", &StreamMinRows::get,
         "M from which linear_fwd / linear_dgrad(_relu) route supported shapes to it");
-  m.def("set_linear_stream_min_rows", &set_linear_stream_min_rows,
+  m.def("set_linear_stream_min_rows", &StreamMinRows::set,
         "override that M (tests); negative restores the measured one; returns the old setting",
         py::arg("rows"));
   m.def("linear_fwd_stream", &linear_fwd_stream,
         "Y = X W^T (+bias)(+relu) through the full-N streaming kernel, any M", py::arg("x"),
         py::arg("w"), py::arg("bias"), py::arg("relu"), py::arg("path") = 0);
-  m.def("linear_fwd_stream_deep_supported",
-        [](int64_t N, int64_t K, int64_t M) {
-          return N <= 256 && K < (1 << 24) &&
-                 linear_fwd_stream_deep_supported((int)N, (int)K, M) != 0;
-        },
+  m.def("linear_fwd_stream_deep_supported", linear_fwd_stream_deep_ok,
         "does the deep-K forward of the streaming kernels (path 2) serve the shape",
         py::arg("N"), py::arg("K"), py::arg("M"));
-  m.def("linear_fwd_stream_deep_min_rows", &linear_stream_deep_min_rows,
+  m.def("linear_fwd_stream_deep_min_rows", &StreamDeepMinRows::get,
         "M from which a routed K > 256 forward takes the deep-K kernel");
-  m.def("set_linear_stream_deep_min_rows", &set_linear_stream_deep_min_rows,
+  m.def("set_linear_stream_deep_min_rows", &StreamDeepMinRows::set,
         "override that M (tests); negative restores the measured one; returns the old setting",
         py::arg("rows"));
   m.def("linear_dgrad_stream", &linear_dgrad_stream,
@@ -1652,25 +1441,25 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "bf16 logits or None)",
         py::arg("x"), py::arg("weights"), py::arg("biases"), py::arg("want_logits") = false,
         py::arg("max_blocks") = 0);
-  m.def("linear_wgrad_stream_supported", &linear_wgrad_stream_ok,
+  m.def("linear_wgrad_stream_supported", linear_wgrad_stream_ok,
         "is (No, Ki) at batch B routed to the batch-streaming wgrad");
-  m.def("linear_wgrad_stream_can_run", &linear_wgrad_stream_runs,
+  m.def("linear_wgrad_stream_can_run", linear_wgrad_stream_runs,
         "can the batch-streaming wgrad compute (No, Ki, B) at all");
   m.def("linear_wgrad_stream", &linear_wgrad_stream,
         "dW (+ db) accumulated by the persistent batch-streaming kernel", py::arg("dz"),
         py::arg("x"), py::arg("dw"), py::arg("db") = py::none(), py::arg("max_blocks") = 0);
-  m.def("linear_wgrad_wide_supported", &linear_wgrad_wide_ok,
+  m.def("linear_wgrad_wide_supported", linear_wgrad_wide_ok,
         "is (No, Ki) at batch B routed to the wide-layer streaming wgrad");
-  m.def("linear_wgrad_wide_can_run", &linear_wgrad_wide_runs,
+  m.def("linear_wgrad_wide_can_run", linear_wgrad_wide_runs,
         "can the wide-layer streaming wgrad compute (No, Ki, B) at all");
   m.def("linear_wgrad_wide", &linear_wgrad_wide,
         "dW (+ db) of a wide layer on a 64/128/256-wide input, accumulated by its persistent "
         "batch-streaming kernel",
         py::arg("dz"), py::arg("x"), py::arg("dw"), py::arg("db") = py::none(),
         py::arg("max_blocks") = 0);
-  m.def("linear_hidden_bwd_supported", &linear_hidden_bwd_ok,
+  m.def("linear_hidden_bwd_supported", linear_hidden_bwd_ok,
         "is (No, Ki) at batch B routed to the one-pass hidden-layer backward");
-  m.def("linear_hidden_bwd_can_run", &linear_hidden_bwd_runs,
+  m.def("linear_hidden_bwd_can_run", linear_hidden_bwd_runs,
         "can the one-pass hidden-layer backward compute (No, Ki, B) at all");
   m.def("linear_hidden_bwd", &linear_hidden_bwd,
         "masked dz_in returned, dW (+ db) accumulated, one pass over dz and x_in", py::arg("dz"),

@@ -6,11 +6,9 @@
 
 #include <cstdint>
 
-#define WAVE 64
+#include "launchers.h"  // bf16raw
 
-// bf16 carried as raw uint16 bits; conversions are explicit bit ops so we do
-// not depend on hip_bf16 operator overloads inside hot loops.
-typedef uint16_t bf16raw;
+#define WAVE 64
 
 __device__ __forceinline__ float bf16_to_f32(bf16raw h) {
   union {

@@ -7,6 +7,7 @@
 // models run through torch on CPU; reference has no GPU/native code at all).
 // All NCHW, bf16 activations.
 
+#include "launchers.h"
 #include "common.h"
 
 static inline int cgrid(int64_t n, int block) {

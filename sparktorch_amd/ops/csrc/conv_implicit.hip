@@ -26,6 +26,7 @@
 // CI % 16 == 0, CO % 8 == 0; wmat column-padded to a multiple of 64.
 // Everything else keeps the explicit im2col path.
 
+#include "launchers.h"
 #include "mfma_tile.h"
 
 #define IC_LDS_PAD 8

@@ -10,6 +10,7 @@
 // col matrix layout: col[(b*HO+ho)*WO+wo, (kh*KW+kw)*CI+ci]  (row-major,
 // K = KH*KW*CI) — matches w2d = w.permute(0,2,3,1).reshape(CO, K).
 
+#include "launchers.h"
 #include "common.h"
 
 static inline int cgrid8(int64_t n, int block) {

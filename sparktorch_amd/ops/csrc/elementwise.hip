@@ -16,6 +16,7 @@
 // All memory-bound: vectorized loads (float4 / 8x bf16), grid-stride loops,
 // grid capped so the scheduler keeps ~8 blocks/CU (guide §6 G11/G13).
 
+#include "launchers.h"
 #include "common.h"
 
 static inline int ew_grid(int64_t work_items, int block) {

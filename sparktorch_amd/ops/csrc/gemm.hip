@@ -43,6 +43,7 @@
 // (ones_row).  The XCD-aware block swizzle keeps an output tile's operand
 // rows inside one XCD's L2.
 
+#include "launchers.h"
 #include "mfma_tile.h"
 
 #define BM 128

@@ -50,6 +50,7 @@
 // fetches its class ids, so they arrive under the y_in DMA and never pass
 // through LDS (profiles/head_mse.md).
 
+#include "launchers.h"
 #include "mfma_tile.h"
 
 #define HEAD_THREADS 256

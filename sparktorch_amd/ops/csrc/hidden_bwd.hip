@@ -42,6 +42,7 @@
 //
 // Built without packed fp32 instructions (ops/build.py).
 
+#include "launchers.h"
 #include "linear_wgrad_tile.h"
 
 #define HB_THREADS 512

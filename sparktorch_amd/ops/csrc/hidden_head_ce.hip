@@ -35,6 +35,7 @@
 // relu(b2), finite, their dlogits are zero and nothing of them is stored.
 // Measurements: profiles/hidden_head_ce.md.
 
+#include "launchers.h"
 #include "mfma_tile.h"
 
 #define HH_THREADS 512

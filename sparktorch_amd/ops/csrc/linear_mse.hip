@@ -47,6 +47,7 @@
 // The translation unit is compiled without packed fp32 instructions
 // (v_pk_*_f32), as hidden_bwd.hip is: dpred keeps mse_fused_kernel's bits.
 
+#include "launchers.h"
 #include "mfma_tile.h"
 
 #define LM_THREADS 512

@@ -32,6 +32,7 @@
 // Rows past M and a K tail take a guarded, zero-filling stage of the same
 // images.  N = 192 leaves wave column 3 idle (it still helps staging).
 
+#include "launchers.h"
 #include "mfma_tile.h"
 
 #define LS_THREADS 512
@@ -465,10 +466,6 @@ extern "C" int64_t linear_fwd_stream_min_rows() { return LS_MIN_ROWS; }
 // block per CU, which loses while the blocks do not fill the chip.
 #define LS_DEEP_MIN_ROWS 65536
 extern "C" int64_t linear_fwd_stream_deep_min_rows() { return LS_DEEP_MIN_ROWS; }
-
-#define LS_PATH_AUTO 0
-#define LS_PATH_TILE128 1  // linear_stream_kernel
-#define LS_PATH_DEEP 2     // linear_stream_deep_kernel
 
 // epi: EPI_BF16 / BIAS / BIAS_RELU / RELU (mfma_tile.h) for the forward
 // (b_kn = 0, B = W[N][K]); EPI_BF16 / EPI_BF16_MASK for the dgrad (b_kn = 1,

@@ -35,6 +35,7 @@
 // linear_wgrad_wide.hip (the mirror image, for No > 256) and hidden_bwd.hip
 // (this decomposition with a hidden layer's masked dgrad added).
 
+#include "launchers.h"
 #include "linear_wgrad_tile.h"
 
 #define LWG_THREADS 256

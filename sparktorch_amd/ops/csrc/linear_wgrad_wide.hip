@@ -40,6 +40,7 @@
 // own: dW is held transposed to linear_wgrad.hip's and db is read in another
 // order.
 
+#include "launchers.h"
 #include "linear_wgrad_tile.h"
 
 #define LWW_THREADS 256

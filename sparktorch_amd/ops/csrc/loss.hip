@@ -5,6 +5,7 @@
 // removes a full re-read of the logits.  Loss is reduced per-block then
 // atomicAdd'ed into a single fp32 scalar (guide §6 G12).
 
+#include "launchers.h"
 #include "common.h"
 
 // ---------------------------------------------------------------------------

@@ -25,25 +25,12 @@
 #pragma once
 
 #include "common.h"
+#include "launchers.h"  // EPI_*: the epilogue codes of gemm_kernel and linear_stream_kernel
 
 typedef shortx8 mt_frag_t;  // 8 bf16 (4 VGPRs): one lane's share of an MFMA operand
 
 // 1.0; a fragment of it as one MFMA operand sums the other operand over k
 #define MT_BF16_ONE ((bf16raw)0x3F80)
-
-// Epilogue codes of gemm_kernel and linear_stream_kernel
-#define EPI_F32 0        // fp32 store (atomicAdd when SPLITK)
-#define EPI_BF16 1       // bf16 store
-#define EPI_BIAS 2       // bf16 store, + bias[n]
-#define EPI_BIAS_RELU 3  // bf16 store, + bias[n], relu
-#define EPI_RELU 4       // bf16 store, relu (no bias)
-#define EPI_F32_SLAB 5   // fp32 per-slice slab store (split-K without atomics;
-                         // a separate reduce kernel combines the slabs —
-                         // guide §5 "splitk-seam": slab reducer beats an
-                         // fp32-atomicAdd accumulator)
-#define EPI_BF16_MASK 6  // bf16 store, zeroed where mask[m][n] <= 0 (mask: bf16
-                         // [M][N], same layout as C) — dgrad with the upstream
-                         // ReLU backward folded in
 
 // ---- waits ----
 

@@ -88,6 +88,7 @@
 //     head (whose mp_publish(0) waits merely land them early); the next tile
 //     starts by converting slab 0.
 
+#include "launchers.h"
 #include "mfma_tile.h"
 
 #define MP_THREADS 512

@@ -16,6 +16,7 @@
 // per-thread scale/shift (6.6 TB/s measured) and recompute the fused-ReLU
 // mask from x instead of reading the saved output.
 
+#include "launchers.h"
 #include "common.h"
 
 // ---------------------------------------------------------------------------

@@ -30,6 +30,7 @@
 // 1568 B rows, not the kernel; half the grid and non-temporal accesses moved
 // it by 3 % or less.
 
+#include "launchers.h"
 #include "common.h"
 
 #define SG_ROUNDS 6
